@@ -30,6 +30,10 @@ Also reported on the same JSON line:
   cpu_baseline        the same PPO iteration through oracle/model_torch.py (plain torch CPU operators — what
                       the reference runs with --device=cpu) on a bounded sample (one 256-observation rollout
                       forward, one 256-sample minibatch), extrapolated to env-steps/s.
+
+`--dump-outputs DIR` writes what the last timed step computed (rollout buffers, returns, parameters after the
+optimiser steps, per-minibatch statistics) as DIR/<name>.npy, so that two builds can be compared output for output:
+the inputs (seeded synthetic envs, seeded initialisation) are the same for the same arguments.
 """
 import argparse
 import json
@@ -76,8 +80,11 @@ CONFIGS = {
 def parse():
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
-    p.add_argument("--steps", type=int, default=3)
+    p.add_argument("--steps", type=int, default=3, help="timed PPO iterations (ms_per_step = their wall time / steps)")
     p.add_argument("--warmup", type=int, default=1)
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64, "
+                        "at most 64 MB; see dump_outputs)")
     p.add_argument("--config", default="pong", choices=sorted(CONFIGS),
                    help="workload: pong = BASELINE.json configs[1] (the driver's line, default); procgen = configs[2]; "
                         "humanoid_tvf = configs[4]")
@@ -781,10 +788,64 @@ def cpu_baseline_mlp(N, A, mb, F, H, n_actions, K, epochs):
 
 
 # ----------------------------------------------------------------------------- main
+DUMP_MAX_ELEMS = 2 << 20        # per array: a larger output is written as a fixed, seeded sample of this many elements
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, runner, model):
+    """--dump-outputs: what the last timed PPO iteration left for its caller, one DIR/<name>.npy per array.
+
+    Rollout buffers (observations, actions, log-probabilities, values, rewards, terminals), the returns pass
+    (advantages, returns, TVF returns), the training pass (per-minibatch statistics and gradient norms, advantage
+    mean / std) and the parameters after the optimiser steps.  float64 arrays stay float64, everything else is
+    written as float32 (uint8 / int32 / bool values are exact there).  An array of more than DUMP_MAX_ELEMS elements
+    is written flattened, as the elements at np.random.default_rng(0).choice(size, DUMP_MAX_ELEMS, replace=False)
+    in ascending index order: the same positions in every run with the same arguments.  Returns what was written."""
+    import numpy as np
+    import torch
+    arrays = {"observations": runner.all_obs, "actions": runner.actions, "log_pac": runner.log_pac,
+              "log_policy": runner.log_policy, "raw_policy": runner.raw_policy, "value": runner.value,
+              "rewards": runner.ext_rewards, "terminals": runner.terminals, "advantage": runner.advantage,
+              "norm_advantage": runner.norm_advantage, "returns": runner.returns,
+              "advantage_mean_std": runner._mean_std}
+    if runner.tvf is not None:
+        arrays["tvf_value"] = runner.tvf.tvf_value
+        arrays["tvf_returns"] = runner.tvf.tvf_returns
+    for label, (stat_rows, norm_rows, _mb) in sorted(runner._phase_stats.items()):
+        arrays[f"{label}_stat_rows"] = stat_rows
+        arrays[f"{label}_grad_norms"] = norm_rows
+    arrays["policy_params"] = model.policy_net.flat
+    if model.value_net is not model.policy_net:
+        arrays["value_params"] = model.value_net.flat
+    if model.obs_norm is not None:
+        arrays["obs_norm_mean"], arrays["obs_norm_var"] = model.obs_norm.mean, model.obs_norm.var
+    host, sampled = {}, []
+    for name, t in arrays.items():
+        t = t.detach()
+        flat = t.reshape(-1)
+        if flat.numel() > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(0).choice(flat.numel(), DUMP_MAX_ELEMS, replace=False))
+            t = flat[torch.from_numpy(idx).to(flat.device)]
+            sampled.append(name)
+        host[name] = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy()
+    total = sum(v.nbytes for v in host.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (limit {DUMP_MAX_BYTES})")
+    os.makedirs(dirname, exist_ok=True)
+    for name, v in host.items():
+        np.save(os.path.join(dirname, name + ".npy"), v)
+    return {"dir": dirname, "arrays": len(host), "bytes": total, "sampled": sampled}
+
+
 def main():
     a = parse()
     if a.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if a.steps < 1:
+        raise SystemExit("bench.py: --steps must be >= 1")
+    if a.dump_outputs and (a.scan_only or a.tvf_only or a.rendezvous_only):
+        raise SystemExit("bench.py: --dump-outputs writes the PPO iteration's outputs; --scan-only, --tvf-only and "
+                         "--rendezvous-only run none")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return launch_ranks(a)
     # first thing in a rank, before any HIP call / thread pool / pinned allocation: the cores of this GPU's NUMA node
@@ -906,6 +967,8 @@ def main():
     probe.enabled = False
     probe.remove()
     stats = runner.fetch_stats()
+    # before the kernel table's extra iteration and the opt-in leg, which run on past the timed steps
+    dumped = dump_outputs(a.dump_outputs, runner, model) if a.dump_outputs and rank == 0 else None
     exposed_comm_ms = reducer.exposed_ms() if reducer is not None else None
 
     env_steps = world * N * A * a.steps
@@ -999,6 +1062,8 @@ def main():
         "model_frac_of_mfma_peak_whole_step": round(model_tflops / world / MFMA_F32_PEAK_TFLOPS, 4),
         "train_stats": {k: round(float(v), 6) for k, v in stats.items()},
     }
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
     if world > 1:
         out["grad_allreduce"] = {"buckets": 2, "exposed_ms_per_optimizer_step": None if exposed_comm_ms is None
                                  else round(exposed_comm_ms, 4),

@@ -516,6 +516,10 @@ class Runner:
         # each env group has its own compute stream (and scratch-buffer set), so the policy steps of the two
         # groups overlap on the GPU: at half the batch most kernels expose fewer workgroups than there are CUs
         streams = self._part_streams if P > 1 else [main]
+        # the optimiser steps leave the packed convolution operands stale and the next forward repacks them on its own
+        # stream; on a group's stream that would race the other group's forward, which reads them: repack here, on main
+        for net in {id(n): n for n in (self.policy_net, self.value_net)}.values():
+            net._refresh_packed()
         copy_stream.wait_stream(main)  # earlier readers of all_obs (the previous train phase) are done
         for s_ in streams:
             if s_ is not main:
