@@ -511,14 +511,16 @@ class DualHeadNet:
         self._mlp_npart = ctypes.c_int(0)
         self.mlp_fused = True
 
-    def _mlp_train(self, kind, prev_state, index, stats, n_stats, stat_sums, stat_accumulate, **fields):
+    def _mlp_train(self, kind, prev_state, index, stats, n_stats, stat_sums, stat_accumulate, *, obs_indexed=False,
+                   **fields):
         """Forward + loss `kind` + backward of one minibatch through the fused launches; the gradients land in
-        self.grad, the per-workgroup sums of g^2 in the optimiser's workspace (adam_step picks them up)."""
-        B = int(index.shape[0]) if index is not None else int(prev_state.shape[0])
+        self.grad, the per-workgroup sums of g^2 in the optimiser's workspace (adam_step picks them up).
+        obs_indexed: prev_state is the array `index` points into (sample b is its row index[b]), see ppo_minibatch."""
+        B = self._minibatch_rows(prev_state, index, obs_indexed)
         x = prev_state
         if x.dtype != torch.float32 or not x.is_contiguous():
             raise ValueError("the mlp encoder takes contiguous float32 observations")
-        x_indexed = int(x.shape[0]) if (index is not None and x.shape[0] != B) else 0  # rows of the whole batch
+        x_indexed = int(x.shape[0]) if obs_indexed else 0  # rows of the array the index points into
         if self.obs_norm is not None:
             if x_indexed:
                 raise ValueError("observation normalisation needs the gathered minibatch")
@@ -1439,8 +1441,22 @@ class DualHeadNet:
             and bool(WGRAD_POOLED_DY and WGRAD_BATCH_REDUCE) \
             and bool(self.lib.ppo_conv3x3_backward_weight_pooled_supported(cin, cout, h, w))
 
-    def _train_forward(self, prev_state, index=None):
-        if index is not None and prev_state.shape[0] != index.shape[0]:
+    @staticmethod
+    def _minibatch_rows(prev_state, index, obs_indexed) -> int:
+        """The number of samples of a training minibatch, after checking that prev_state is what obs_indexed says."""
+        if obs_indexed:
+            if index is None:
+                raise ValueError("obs_indexed=True needs the index that prev_state is read through")
+            return int(index.shape[0])
+        B = int(prev_state.shape[0])
+        if index is not None and int(index.shape[0]) != B:
+            raise ValueError(f"prev_state holds {B} rows for a minibatch of {int(index.shape[0])}: pass the gathered "
+                             "minibatch, or the array the index points into with obs_indexed=True")
+        return B
+
+    def _train_forward(self, prev_state, index=None, obs_indexed=False):
+        self._minibatch_rows(prev_state, index, obs_indexed)
+        if obs_indexed:
             if not self.takes_obs_index(prev_state):
                 raise ValueError("this net needs the gathered minibatch of observations (takes_obs_index is False)")
             self.obs_index = index
@@ -1454,23 +1470,28 @@ class DualHeadNet:
 
     def ppo_minibatch(self, prev_state, actions, old_log_pac, old_log_policy, advantages, returns,
                       eps_clip=0.2, ent_coef=0.01, vf_coef=0.5, loss_scale=1.0, index=None, stat_sums=None,
-                      stat_accumulate=False):
+                      stat_accumulate=False, obs_indexed=False):
         """Forward, fused PPO loss, backward: gradients of mean(-gain)*loss_scale land in self.grad
         (Runner.train_policy_minibatch, rl/rollout.py:1610-1771; discrete actions).  vf_coef = 0 (and
         returns None) leaves the value head out, as the dual architecture's policy phase does (:1744).
-        prev_state is the (already gathered) minibatch of observations; the per-sample arrays are
-        either minibatch-sized or, with ``index`` ([B] int32), whole-batch arrays read at index[b].
+        The per-sample arrays are either minibatch-sized or, with ``index`` ([B] int32), whole-batch arrays read at
+        index[b].  What prev_state holds is said by ``obs_indexed``, never inferred from its shape:
+        False - exactly the minibatch's rows, in order (already gathered); ``index`` then applies to the per-sample
+        arrays only, and a prev_state whose row count is not B raises ValueError.
+        True - the array ``index`` points into: sample b is prev_state[index[b]] and B = len(index), whatever
+        prev_state.shape[0] is (B included).  Needs ``index``, and a net that can read through it (takes_obs_index,
+        or the fused MLP path without observation normalisation); anything else raises ValueError.
         Returns the per-sample statistics tensor [B, 8] (device).  MLP nets on the fused path (mlp_fused) also take
-        the whole batch of observations as prev_state (rows read through ``index``) and ``stat_sums``, a device row
-        that receives the column sums of the statistics."""
+        ``stat_sums``, a device row that receives the column sums of the statistics."""
         if self.mlp_fused:
-            B = int(index.shape[0]) if index is not None else int(prev_state.shape[0])
+            B = self._minibatch_rows(prev_state, index, obs_indexed)
             return self._mlp_train(
                 _lib.MLP_LOSS_PPO, prev_state, index, self._buf("loss_stats", (B, 8)), 8, stat_sums, stat_accumulate,
-                grad_scale=float(loss_scale) / B, n_actions=self.n_actions, n_value_heads=self.vh if returns is not None else 0,
+                obs_indexed=obs_indexed, grad_scale=float(loss_scale) / B, n_actions=self.n_actions,
+                n_value_heads=self.vh if returns is not None else 0,
                 returns=_p(returns), vf_coef=float(vf_coef), actions_i=_p(actions), old_log_pac=_p(old_log_pac),
                 old_log_policy=_p(old_log_policy), advantages=_p(advantages), eps_clip=float(eps_clip), ent_coef=float(ent_coef))
-        B = int(index.shape[0]) if index is not None else int(prev_state.shape[0])
+        B = self._minibatch_rows(prev_state, index, obs_indexed)
         stats = self._buf("loss_stats", (B, 8))
         vh = self.vh if returns is not None else 0
         loss_args = (self.n_actions, vh, _p(actions), _p(old_log_pac), _p(old_log_policy), _p(advantages), _p(returns),
@@ -1479,7 +1500,7 @@ class DualHeadNet:
         # the loss rides on the dense + heads launch of the training forward where that launch exists (IMPALA, relu)
         self.loss_tail = loss_args if FUSE_LOSS else None
         try:
-            acts, o, B, dheads = self._train_forward(prev_state, index)
+            acts, o, B, dheads = self._train_forward(prev_state, index, obs_indexed)
             fused = FUSE_LOSS and self.loss_tail is None
         finally:
             self.loss_tail = None
@@ -1489,17 +1510,19 @@ class DualHeadNet:
         return stats
 
     def gaussian_minibatch(self, prev_state, actions, old_log_pac, advantages, returns, eps_clip=0.2, vf_coef=0.5,
-                           loss_scale=1.0, index=None, stat_sums=None, stat_accumulate=False):
-        """As ppo_minibatch for gaussian policies (rl/rollout.py:1693-1704); also fills log_std's gradient."""
+                           loss_scale=1.0, index=None, stat_sums=None, stat_accumulate=False, obs_indexed=False):
+        """As ppo_minibatch for gaussian policies (rl/rollout.py:1693-1704); also fills log_std's gradient.
+        prev_state, ``index`` and ``obs_indexed`` as in ppo_minibatch."""
         if self.mlp_fused:
-            B = int(index.shape[0]) if index is not None else int(prev_state.shape[0])
+            B = self._minibatch_rows(prev_state, index, obs_indexed)
             return self._mlp_train(
                 _lib.MLP_LOSS_GAUSSIAN, prev_state, index, self._buf("loss_stats", (B, 8)), 8, stat_sums, stat_accumulate,
-                grad_scale=float(loss_scale) / B, n_actions=self.n_actions, n_value_heads=self.vh if returns is not None else 0,
+                obs_indexed=obs_indexed, grad_scale=float(loss_scale) / B, n_actions=self.n_actions,
+                n_value_heads=self.vh if returns is not None else 0,
                 returns=_p(returns), vf_coef=float(vf_coef), actions_f=_p(actions), old_log_pac=_p(old_log_pac),
                 advantages=_p(advantages), log_std=_p(self.params["log_std"]), eps_clip=float(eps_clip),
                 dlog_std_rows=_p(self._buf("dlog_std_rows", (B, self.n_actions))))
-        acts, o, B, dheads = self._train_forward(prev_state, index)
+        acts, o, B, dheads = self._train_forward(prev_state, index, obs_indexed)
         stats = self._buf("loss_stats", (B, 8))
         rows = self._buf("dlog_std_rows", (B, self.n_actions))
         vh = self.vh if returns is not None else 0
@@ -1513,19 +1536,21 @@ class DualHeadNet:
 
     def value_minibatch(self, prev_state, returns=None, tvf_returns=None, tvf_weights=None, vf_coef=0.5,
                         tvf_coef=1.0, loss_scale=1.0, index=None, tvf_keep_prob=1.0, dropout_seed=0, dropout_offset=0,
-                        stat_sums=None, stat_accumulate=False):
+                        stat_sums=None, stat_accumulate=False, obs_indexed=False):
         """Value phase (Runner.train_value_minibatch, rl/rollout.py:1513-1567; TVF loss rl/tvf.py:32-77, with
-        horizon dropout when tvf_keep_prob < 1: :64-69)."""
+        horizon dropout when tvf_keep_prob < 1: :64-69).  prev_state, ``index`` and ``obs_indexed`` as in
+        ppo_minibatch."""
         if self.mlp_fused:
-            B = int(index.shape[0]) if index is not None else int(prev_state.shape[0])
+            B = self._minibatch_rows(prev_state, index, obs_indexed)
             return self._mlp_train(
                 _lib.MLP_LOSS_VALUE, prev_state, index, self._buf("value_stats", (B, 4)), 4, stat_sums, stat_accumulate,
-                grad_scale=float(loss_scale) / B, value_col=self.col_value, n_value_heads=self.vh if returns is not None else 0,
+                obs_indexed=obs_indexed, grad_scale=float(loss_scale) / B, value_col=self.col_value,
+                n_value_heads=self.vh if returns is not None else 0,
                 returns=_p(returns), vf_coef=float(vf_coef), tvf_col=self.col_tvf if self.K else 0,
                 n_tvf=self.K if tvf_returns is not None else 0, tvf_stride=max(self.vh, 1), tvf_returns=_p(tvf_returns),
                 tvf_weights=_p(tvf_weights), tvf_coef=float(tvf_coef), tvf_keep_prob=float(tvf_keep_prob),
                 seed=int(dropout_seed) & (2**64 - 1), offset=int(dropout_offset) & (2**64 - 1))
-        acts, o, B, dheads = self._train_forward(prev_state, index)
+        acts, o, B, dheads = self._train_forward(prev_state, index, obs_indexed)
         stats = self._buf("value_stats", (B, 4))
         self._call("ppo_value_loss_f32", _p(o), B, self.nh, self.col_value, self.vh if returns is not None else 0,
                    _p(returns), float(vf_coef), self.col_tvf if self.K else 0, self.K if tvf_returns is not None else 0,
@@ -1536,18 +1561,20 @@ class DualHeadNet:
         return stats
 
     def distil_minibatch(self, prev_state, targets, old_policy, beta=1.0, use_tvf=False, weights=None, gaussian=False,
-                         loss_scale=1.0, index=None, stat_sums=None, stat_accumulate=False):
+                         loss_scale=1.0, index=None, stat_sums=None, stat_accumulate=False, obs_indexed=False):
         """Distillation phase (Runner.train_distil_minibatch, rl/rollout.py:1331-1449): targets [*] against the
-        ext value head, or [*, K] against the TVF heads' ext column (use_tvf)."""
+        ext value head, or [*, K] against the TVF heads' ext column (use_tvf).  prev_state, ``index`` and
+        ``obs_indexed`` as in ppo_minibatch."""
         col, n_pred, stride = (self.col_tvf, self.K, self.vh) if use_tvf else (self.col_value, 1, 1)
         if self.mlp_fused:
-            B = int(index.shape[0]) if index is not None else int(prev_state.shape[0])
+            B = self._minibatch_rows(prev_state, index, obs_indexed)
             return self._mlp_train(
                 _lib.MLP_LOSS_DISTIL, prev_state, index, self._buf("distil_stats", (B, 4)), 4, stat_sums, stat_accumulate,
-                grad_scale=float(loss_scale) / B, n_actions=self.n_actions, pred_col=col, n_pred=n_pred, pred_stride=stride,
+                obs_indexed=obs_indexed, grad_scale=float(loss_scale) / B, n_actions=self.n_actions, pred_col=col,
+                n_pred=n_pred, pred_stride=stride,
                 vector_targets=1 if use_tvf else 0, targets=_p(targets), weights=_p(weights), old_policy=_p(old_policy),
                 log_std=_p(self.params["log_std"]) if gaussian else None, beta=float(beta))
-        acts, o, B, dheads = self._train_forward(prev_state, index)
+        acts, o, B, dheads = self._train_forward(prev_state, index, obs_indexed)
         stats = self._buf("distil_stats", (B, 4))
         self._call("ppo_distil_loss_f32", _p(o), B, self.nh, self.n_actions, col, n_pred, stride, 1 if use_tvf else 0,
                    _p(targets), _p(weights), _p(old_policy), _p(self.params["log_std"]) if gaussian else None,

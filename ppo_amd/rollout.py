@@ -843,11 +843,12 @@ class Runner:
                     for u in range(n_micro):
                         idx = order_dev[j * mb + u * micro:j * mb + (u + 1) * micro]
                         if fused:
-                            step_fn(obs_rows, idx, 1.0 / n_micro, stat_sums=stat_rows[k], stat_accumulate=bool(u))
+                            step_fn(obs_rows, idx, 1.0 / n_micro, stat_sums=stat_rows[k], stat_accumulate=bool(u),
+                                    obs_indexed=True)
                             acc.after_backward()
                             continue
                         if in_conv:
-                            stats = step_fn(obs_all, idx, 1.0 / n_micro)
+                            stats = step_fn(obs_all, idx, 1.0 / n_micro, obs_indexed=True)
                         else:
                             self._call("ppo_gather_rows", _p(obs_rows), row_bytes, B, _p(idx), micro, _p(mb_obs))
                             stats = step_fn(mb_obs, idx, 1.0 / n_micro)

@@ -159,7 +159,7 @@ def test_minibatch_read_through_the_permutation_equals_the_gathered_minibatch():
     orig = net._call
     net._call = lambda fn, *a: (calls.append(fn), orig(fn, *a))[1]
     net.grad.zero_()
-    s_i = net.ppo_minibatch(obs, actions, pac, lp, adv, ret, index=idx).clone()
+    s_i = net.ppo_minibatch(obs, actions, pac, lp, adv, ret, index=idx, obs_indexed=True).clone()
     torch.cuda.synchronize()
     assert "ppo_conv3x3_pool_forward_packed_indexed_f32" in calls and "ppo_conv3x3_backward_weight_slabs_pooled_indexed_f32" in calls
     assert torch.equal(s_g, s_i) and torch.equal(g_g, net.grad) and float(g_g.abs().max()) > 0
