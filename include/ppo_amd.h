@@ -250,6 +250,48 @@ int ppo_maxpool3x3s2_forward_f32(const float *in, float *out, uint8_t *argmax, i
 int ppo_maxpool3x3s2_backward_f32(const float *dout, const uint8_t *argmax, float *din, int n, int c, int h, int w,
                                   void *stream);
 
+/* ------------------------------------------------------------------------
+ * Strided convolutions without padding, any geometry (csrc/conv_strided.hip): the layers of the reference's
+ * NatureCNN (rl/models.py:101-145: conv1 8x8 stride 4, conv2 4x4 stride 2, conv3 3x3 stride 1, F.relu behind each,
+ * :135-137) and their autograd.  Implicit GEMMs on the exact-f32 MFMA, f32 accumulation in a fixed order: every
+ * launch gives the same bits.  Activations NCHW, weights [cout, cin, kh, kw] (PyTorch layout), contiguous;
+ * ho = (h - kh) / stride + 1, wo = (w - kw) / stride + 1.  Geometry arguments are always those of the FORWARD
+ * convolution.
+ *
+ * ppo_conv2d_strided_supported: 1 when a geometry has a kernel (all extents >= 1, the window inside the image,
+ *   channels and image sides <= 4096, kernel sides and stride <= 16), else 0.  What it rejects - and a batch n < 1 or
+ *   a tensor of 2^30 elements or more - every entry point below rejects with PPO_E_INVALID before any HIP call.
+ * ---------------------------------------------------------------------- */
+int ppo_conv2d_strided_supported(int cin, int cout, int kh, int kw, int stride, int h, int w);
+/*
+ * out[n,o,y,x] = f( bias[o] + sum_{i,ky,kx} in[n,i,y*stride+ky,x*stride+kx] * weight[o,i,ky,kx] ),  f = max(., 0) when
+ * relu_out, else the identity (torch.nn.Conv2d + F.relu, rl/models.py:114-116, 135-137).  in_mode: PPO_IN_NONE
+ * (float32) or PPO_IN_U8 (uint8 observation, x / 255 on load, rl/models.py:842-848).  bias nullable.
+ * FLOPs: 2 * cin*kh*kw * cout * ho*wo per image.
+ */
+int ppo_conv2d_strided_forward_f32(const void *in, int in_mode, const float *weight, const float *bias, float *out,
+                                   int relu_out, int n, int cin, int h, int w, int cout, int kh, int kw, int stride,
+                                   void *stream);
+/*
+ * Gradient w.r.t. the input (autograd of the same nn.Conv2d), gather form - each dx element sums the taps that reach it:
+ *   dx[n,i,y,x] = sum_{o,ky,kx : y = oy*stride+ky, x = ox*stride+kx} g[n,o,oy,ox] * weight[o,i,ky,kx]
+ * g = dy where gate > 0, else 0; gate (nullable: g = dy) is the forward's post-ReLU output [n,cout,ho,wo], so the
+ * F.relu behind the convolution is differentiated in the same launch (derivative 0 at 0, as torch's).
+ */
+int ppo_conv2d_strided_backward_data_f32(const float *dy, const float *gate, const float *weight, float *dx, int n,
+                                         int cin, int h, int w, int cout, int kh, int kw, int stride, void *stream);
+/*
+ * Weight and bias gradient:  dweight[o,i,ky,kx] = sum_{n,oy,ox} g[n,o,oy,ox] * in[n,i,oy*stride+ky,ox*stride+kx],
+ * dbias[o] = sum g[n,o,oy,ox] (nullable), g and gate as above, `in` / in_mode the forward's input.  The sum over
+ * (n, oy, ox) is cut into slabs, one per workgroup row, whose partial results (dbias among them: one pass over dy) go
+ * to `workspace` - at least ppo_conv2d_strided_wgrad_workspace_bytes(...) bytes - and are added up in ascending order
+ * by a second launch: two calls on the same inputs give the same bits.  Overwrites dweight / dbias.
+ */
+size_t ppo_conv2d_strided_wgrad_workspace_bytes(int n, int cin, int h, int w, int cout, int kh, int kw, int stride);
+int ppo_conv2d_strided_backward_weight_f32(const void *in, int in_mode, const float *dy, const float *gate, float *dweight,
+                                           float *dbias, void *workspace, size_t workspace_bytes, int n, int cin, int h,
+                                           int w, int cout, int kh, int kw, int stride, void *stream);
+
 /*
  * C[m,n] = epi( sum_k fa(A[m,k]) * fb(B[k,n]) + bias[n] ),  f32 MFMA.
  * A element (m,k) at A[m*a_sm + k*a_sk]; B element (k,n) at B[k*b_sk + n*b_sn]; C row-major with ldc.

@@ -130,6 +130,11 @@ SIGNATURES = {
     "ppo_mlp_forward_f32": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "ppo_mlp_train_workspace_floats": (_sz, [_i, _i, _i, _i]),
     "ppo_mlp_train_f32": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "ppo_conv2d_strided_supported": (_i, [_i, _i, _i, _i, _i, _i, _i]),
+    "ppo_conv2d_strided_forward_f32": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "ppo_conv2d_strided_backward_data_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "ppo_conv2d_strided_wgrad_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i, _i]),
+    "ppo_conv2d_strided_backward_weight_f32": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "ppo_adam_step_scatter_f32": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _d, _d, _d, _d, _f, _f, _vp, _vp, _vp, _i64, _vp, _vp]),
 }
 

@@ -68,7 +68,7 @@ class OptimizerConfig(_Group):  # rl/config.py:249-311
 class ModelConfig(_Group):  # rl/config.py:458-476
     FIELDS = (
         ("architecture", str, "dual", "[dual|single]  (north-star PPO = single)"),
-        ("encoder", str, "nature", "[impala|mlp]  (nature has no HIP path)"),
+        ("encoder", str, "nature", "[nature|impala|mlp]"),
         ("encoder_args", str, None, "dict of encoder arguments"),
         ("hidden_units", int, 256, "encoder output features"),
         ("head_scale", float, 0.1, "orthogonal-init gain of the heads"),

@@ -1,0 +1,300 @@
+// Strided "valid" convolutions of any geometry as implicit GEMMs on the exact-f32 MFMA (v_mfma_f32_16x16x4_f32):
+// the layers of the reference's NatureCNN (rl/models.py:101-145: 8x8 stride 4, 4x4 stride 2, 3x3 stride 1, no
+// padding), forward, backward-data and backward-weight.  One kernel, three operand descriptions (csrc/
+// conv_strided_index.h holds the offset arithmetic and the GEMM views).
+//
+// Tile: a workgroup of four waves forms 64 x 32 of C; wave v owns rows 16 v .. 16 v + 15 as two 16 x 16 accumulators
+// (two independent MFMA chains per wave).  K goes through LDS 16 at a time: thread t gathers column t & 15 of the K
+// tile for rows (t >> 4) + 16 j of A (j < 4) and of B^T (j < 2) - global loads of a tile are issued before the barrier
+// that retires the previous tile's reads - into [row][17] images: rows 17 floats apart put the 16 rows x 2 columns of
+// one 32-lane half of a ds_read_b32 operand fetch on 32 different banks (one pair aside), and the writes likewise.
+// Every global access is predicated on its own bounds: rows past M, columns past N and the K tail read as zeros and
+// are never stored.  A sum over K is formed in blocks - the 16 products of a K tile in one MFMA chain, eight tiles, then
+// the groups of eight - which keeps the rounding error of a K = 1024 sum near that of a K = 100 chain; the order is
+// fixed (tiles and slabs ascending): no atomics, the same bits on every launch.
+#include "common.h"
+#include "conv_stage.h"
+#include "conv_strided_index.h"
+#include "mfma.h"
+
+namespace ppo {
+namespace {
+
+constexpr int kTM = 64, kTN = 32, kTK = 16, kLd = kTK + 1, kThreads = 256;
+constexpr int kMaxSlabs = 64;
+constexpr int kFold = 8;  // K tiles per level of the blocked summation
+
+__device__ __forceinline__ float load_in(const void *in, int in_mode, long long off)
+{
+    return in_mode == PPO_IN_U8 ? u8_unit((float)static_cast<const uint8_t *>(in)[off])
+                                : static_cast<const float *>(in)[off];
+}
+__device__ __forceinline__ float load_gated(const float *dy, const float *gate, long long off)
+{
+    const float v = dy[off];
+    return (gate == nullptr || gate[off] > 0.0f) ? v : 0.0f;  // the reference's ReLU has derivative 0 at 0
+}
+
+// out[m, co] = sum_k im2col(in)[m, k] * weight[co, k] + bias[co]
+struct ForwardOp {
+    csi::Geom g;
+    const void *in;
+    int in_mode;
+    const float *weight, *bias;
+    float *out;
+    int relu_out;
+    int M, N, K;
+    struct KCtx {
+        long long a_off;
+        int k;
+    };
+    typedef long long ARow;
+    typedef long long BCol;
+    __device__ void k_range(int, int &kb, int &ke) const { kb = 0, ke = K; }
+    __device__ ARow a_row(int m) const { return csi::in_row_base(g, m); }
+    __device__ BCol b_col(int n) const { return csi::weight_off(g, n, 0); }
+    __device__ KCtx k_ctx(int k) const { return KCtx{csi::in_col_off(g, k), k}; }
+    __device__ float load_a(ARow r, const KCtx &kc) const { return load_in(in, in_mode, r + kc.a_off); }
+    __device__ float load_b(BCol c, const KCtx &kc) const { return weight[c + kc.k]; }
+    __device__ void store(int m, int n, float v, int) const
+    {
+        if (bias != nullptr) v += bias[n];
+        if (relu_out) v = fmaxf(v, 0.0f);
+        out[csi::out_row_base(g, m) + csi::out_col_off(g, n)] = v;
+    }
+};
+
+// dx[m, ci] = sum_{k = (co, ky, kx)} [tap k reaches m] (gate > 0 ? dy : 0)[img, co, oy, ox] * weight[co, ci, ky, kx]
+struct BackwardDataOp {
+    csi::Geom g;
+    const float *dy, *gate, *weight;
+    float *dx;
+    int M, N, K;
+    typedef csi::DxTap KCtx;
+    typedef csi::DxRow ARow;
+    typedef long long BCol;
+    __device__ void k_range(int, int &kb, int &ke) const { kb = 0, ke = K; }
+    __device__ ARow a_row(int m) const { return csi::dx_row(g, m); }
+    __device__ BCol b_col(int n) const { return csi::dx_weight_col_off(g, n); }
+    __device__ KCtx k_ctx(int k) const { return csi::dx_tap(g, k); }
+    __device__ float load_a(const ARow &r, const KCtx &t) const
+    {
+        long long off;
+        return csi::dx_tap_hits(g, r, t, &off) ? load_gated(dy, gate, off) : 0.0f;
+    }
+    __device__ float load_b(BCol c, const KCtx &t) const { return weight[t.w_base + c]; }
+    __device__ void store(int m, int n, float v, int) const
+    {
+        const int img = m / (g.h * g.w), pix = m % (g.h * g.w);
+        dx[(long long)img * g.cin * g.h * g.w + pix + csi::dx_col_off(g, n)] = v;
+    }
+};
+
+// slab z: ws[z, co, kf] = sum_{m in slab z} (gate > 0 ? dy : 0)[m, co] * im2col(in)[m, kf];  kf == K_fwd: the row of
+// ones, i.e. the slab's share of dbias
+struct BackwardWeightOp {
+    csi::Geom g;
+    const void *in;
+    int in_mode;
+    const float *dy, *gate;
+    float *ws;
+    int rows;      // per slab
+    int M_fwd;     // reduction length
+    int M, N;      // K_fwd + 1, cout
+    struct KCtx {
+        long long in_base, out_base;
+    };
+    typedef long long ARow;  // < 0: the row of ones
+    typedef long long BCol;
+    __device__ void k_range(int z, int &kb, int &ke) const { kb = csi::slab_begin(z, rows), ke = csi::slab_end(M_fwd, z, rows); }
+    __device__ ARow a_row(int m) const { return m < M - 1 ? csi::in_col_off(g, m) : -1; }
+    __device__ BCol b_col(int n) const { return csi::out_col_off(g, n); }
+    __device__ KCtx k_ctx(int k) const { return KCtx{csi::in_row_base(g, k), csi::out_row_base(g, k)}; }
+    __device__ float load_a(ARow r, const KCtx &kc) const { return r < 0 ? 1.0f : load_in(in, in_mode, kc.in_base + r); }
+    __device__ float load_b(BCol c, const KCtx &kc) const { return load_gated(dy, gate, kc.out_base + c); }
+    __device__ void store(int m, int n, float v, int z) const { ws[csi::slab_off(g, z, n, m)] = v; }
+};
+
+template <class Op>
+__global__ __launch_bounds__(kThreads) void strided_gemm_kernel(const Op op)
+{
+    __shared__ float s_a[kTM][kLd];
+    __shared__ float s_b[kTN][kLd];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int m0 = blockIdx.x * kTM, n0 = blockIdx.y * kTN;
+    int k_begin, k_end;
+    op.k_range(blockIdx.z, k_begin, k_end);
+    const int kk = tid & 15, r0 = tid >> 4;
+
+    typename Op::ARow a_row[4];
+    bool a_ok[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int m = m0 + r0 + 16 * j;
+        a_ok[j] = m < op.M;
+        a_row[j] = op.a_row(a_ok[j] ? m : 0);
+    }
+    typename Op::BCol b_col[2];
+    bool b_ok[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int n = n0 + r0 + 16 * j;
+        b_ok[j] = n < op.N;
+        b_col[j] = op.b_col(b_ok[j] ? n : 0);
+    }
+
+    const f32x4 zero = {0.0f, 0.0f, 0.0f, 0.0f};
+    f32x4 sum0 = zero, sum1 = zero, mid0 = zero, mid1 = zero;
+    int tiles = 0;
+    for (int k0 = k_begin; k0 < k_end; k0 += kTK) {
+        const int k = k0 + kk;
+        const bool k_ok = k < k_end;
+        const typename Op::KCtx kc = op.k_ctx(k_ok ? k : k_begin);
+        float a[4], b[2];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) a[j] = (k_ok && a_ok[j]) ? op.load_a(a_row[j], kc) : 0.0f;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) b[j] = (k_ok && b_ok[j]) ? op.load_b(b_col[j], kc) : 0.0f;
+        __syncthreads();  // the previous tile has been read
+#pragma unroll
+        for (int j = 0; j < 4; ++j) s_a[r0 + 16 * j][kk] = a[j];
+#pragma unroll
+        for (int j = 0; j < 2; ++j) s_b[r0 + 16 * j][kk] = b[j];
+        __syncthreads();
+        f32x4 acc0 = zero, acc1 = zero;
+#pragma unroll
+        for (int s = 0; s < kTK / 4; ++s) {
+            const float av = s_a[wave * 16 + (lane & 15)][s * 4 + (lane >> 4)];
+            const float b0 = s_b[lane & 15][s * 4 + (lane >> 4)];
+            const float b1 = s_b[16 + (lane & 15)][s * 4 + (lane >> 4)];
+            acc0 = mfma16(av, b0, acc0);
+            acc1 = mfma16(av, b1, acc1);
+        }
+        // blocked summation: a K tile's 16 products, then kFold tiles, then the folds
+        mid0 += acc0, mid1 += acc1;
+        if (++tiles == kFold) {
+            sum0 += mid0, sum1 += mid1;
+            mid0 = zero, mid1 = zero;
+            tiles = 0;
+        }
+    }
+    sum0 += mid0, sum1 += mid1;
+    // lane l holds C[(l >> 4) * 4 + r][l & 15] of each 16 x 16 block in element r
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int m = m0 + wave * 16 + (lane >> 4) * 4 + r;
+        const int n = n0 + (lane & 15);
+        if (m < op.M && n < op.N) op.store(m, n, sum0[r], blockIdx.z);
+        if (m < op.M && n + 16 < op.N) op.store(m, n + 16, sum1[r], blockIdx.z);
+    }
+}
+
+// dweight[co, k] = sum_s ws[s, co, k] (k < K), dbias[co] = sum_s ws[s, co, K], slabs in ascending order
+__global__ __launch_bounds__(256) void strided_wgrad_reduce_kernel(const float *__restrict__ ws, float *__restrict__ dweight,
+                                                                   float *__restrict__ dbias, int n_slabs, int cout, int K)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    const long long per_slab = (long long)cout * (K + 1);
+    if (i >= per_slab) return;
+    float sum = 0.0f;
+    for (int s = 0; s < n_slabs; ++s) sum += ws[s * per_slab + i];
+    const int co = (int)(i / (K + 1)), k = (int)(i % (K + 1));
+    if (k < K)
+        dweight[(long long)co * K + k] = sum;
+    else if (dbias != nullptr)
+        dbias[co] = sum;
+}
+
+int check_geometry(const char *what, int n, int cin, int h, int w, int cout, int kh, int kw, int stride, csi::Geom *g)
+{
+    if (!csi::geometry_ok(cin, cout, kh, kw, stride, h, w))
+        return fail(PPO_E_INVALID, "%s: unsupported geometry cin=%d cout=%d k=%dx%d stride=%d on %dx%d", what, cin, cout, kh,
+                    kw, stride, h, w);
+    *g = csi::make_geom(n, cin, h, w, cout, kh, kw, stride);
+    if (!csi::sizes_ok(*g)) return fail(PPO_E_INVALID, "%s: n=%d is not positive or a tensor exceeds 2^30 elements", what, n);
+    return PPO_OK;
+}
+
+int wgrad_slabs(const csi::Geom &g, int *rows)
+{
+    *rows = csi::slab_rows(csi::fwd_m(g), kMaxSlabs, kTK);
+    return csi::slab_count(csi::fwd_m(g), *rows);
+}
+
+inline dim3 gemm_grid(int M, int N, int Z) { return dim3((M + kTM - 1) / kTM, (N + kTN - 1) / kTN, Z); }
+
+}  // namespace
+}  // namespace ppo
+
+using namespace ppo;
+
+extern "C" int ppo_conv2d_strided_supported(int cin, int cout, int kh, int kw, int stride, int h, int w)
+{
+    return csi::geometry_ok(cin, cout, kh, kw, stride, h, w) ? 1 : 0;
+}
+
+extern "C" int ppo_conv2d_strided_forward_f32(const void *in, int in_mode, const float *weight, const float *bias, float *out,
+                                              int relu_out, int n, int cin, int h, int w, int cout, int kh, int kw, int stride,
+                                              void *stream)
+{
+    csi::Geom g;
+    if (int rc = check_geometry("ppo_conv2d_strided_forward_f32", n, cin, h, w, cout, kh, kw, stride, &g)) return rc;
+    if (in == nullptr || weight == nullptr || out == nullptr)
+        return fail(PPO_E_INVALID, "ppo_conv2d_strided_forward_f32: null pointer");
+    if (in_mode != PPO_IN_NONE && in_mode != PPO_IN_U8)
+        return fail(PPO_E_INVALID, "ppo_conv2d_strided_forward_f32: in_mode %d (PPO_IN_NONE | PPO_IN_U8)", in_mode);
+    ForwardOp op{g, in, in_mode, weight, bias, out, relu_out ? 1 : 0, csi::fwd_m(g), cout, csi::fwd_k(g)};
+    hipLaunchKernelGGL(strided_gemm_kernel<ForwardOp>, gemm_grid(op.M, op.N, 1), dim3(kThreads), 0, as_stream(stream), op);
+    return check_launch("ppo_conv2d_strided_forward_f32");
+}
+
+extern "C" int ppo_conv2d_strided_backward_data_f32(const float *dy, const float *gate, const float *weight, float *dx, int n,
+                                                    int cin, int h, int w, int cout, int kh, int kw, int stride, void *stream)
+{
+    csi::Geom g;
+    if (int rc = check_geometry("ppo_conv2d_strided_backward_data_f32", n, cin, h, w, cout, kh, kw, stride, &g)) return rc;
+    if (dy == nullptr || weight == nullptr || dx == nullptr)
+        return fail(PPO_E_INVALID, "ppo_conv2d_strided_backward_data_f32: null pointer");
+    BackwardDataOp op{g, dy, gate, weight, dx, csi::dx_m(g), cin, csi::dx_k(g)};
+    hipLaunchKernelGGL(strided_gemm_kernel<BackwardDataOp>, gemm_grid(op.M, op.N, 1), dim3(kThreads), 0, as_stream(stream), op);
+    return check_launch("ppo_conv2d_strided_backward_data_f32");
+}
+
+extern "C" size_t ppo_conv2d_strided_wgrad_workspace_bytes(int n, int cin, int h, int w, int cout, int kh, int kw, int stride)
+{
+    if (!csi::geometry_ok(cin, cout, kh, kw, stride, h, w)) return 0;
+    const csi::Geom g = csi::make_geom(n, cin, h, w, cout, kh, kw, stride);
+    if (!csi::sizes_ok(g)) return 0;
+    int rows;
+    const int slabs = wgrad_slabs(g, &rows);
+    return (size_t)slabs * cout * (csi::fwd_k(g) + 1) * sizeof(float);
+}
+
+extern "C" int ppo_conv2d_strided_backward_weight_f32(const void *in, int in_mode, const float *dy, const float *gate,
+                                                      float *dweight, float *dbias, void *workspace, size_t workspace_bytes,
+                                                      int n, int cin, int h, int w, int cout, int kh, int kw, int stride,
+                                                      void *stream)
+{
+    csi::Geom g;
+    if (int rc = check_geometry("ppo_conv2d_strided_backward_weight_f32", n, cin, h, w, cout, kh, kw, stride, &g)) return rc;
+    if (in == nullptr || dy == nullptr || dweight == nullptr || workspace == nullptr)
+        return fail(PPO_E_INVALID, "ppo_conv2d_strided_backward_weight_f32: null pointer");
+    if (in_mode != PPO_IN_NONE && in_mode != PPO_IN_U8)
+        return fail(PPO_E_INVALID, "ppo_conv2d_strided_backward_weight_f32: in_mode %d (PPO_IN_NONE | PPO_IN_U8)", in_mode);
+    int rows;
+    const int slabs = wgrad_slabs(g, &rows);
+    const int K = csi::fwd_k(g);
+    const size_t need = (size_t)slabs * cout * (K + 1) * sizeof(float);
+    if (workspace_bytes < need)
+        return fail(PPO_E_INVALID, "ppo_conv2d_strided_backward_weight_f32: workspace of %zu bytes, %zu needed", workspace_bytes,
+                    need);
+    if (!aligned(workspace, 4)) return fail(PPO_E_ALIGN, "ppo_conv2d_strided_backward_weight_f32: workspace not 4-byte aligned");
+    BackwardWeightOp op{g, in, in_mode, dy, gate, static_cast<float *>(workspace), rows, csi::fwd_m(g), K + 1, cout};
+    hipLaunchKernelGGL(strided_gemm_kernel<BackwardWeightOp>, gemm_grid(op.M, op.N, slabs), dim3(kThreads), 0, as_stream(stream),
+                       op);
+    if (int rc = check_launch("ppo_conv2d_strided_backward_weight_f32")) return rc;
+    const long long per_slab = (long long)cout * (K + 1);
+    hipLaunchKernelGGL(strided_wgrad_reduce_kernel, dim3((unsigned)((per_slab + 255) / 256)), dim3(256), 0, as_stream(stream),
+                       static_cast<const float *>(workspace), dweight, dbias, slabs, cout, K);
+    return check_launch("ppo_conv2d_strided_backward_weight_f32 (reduce)");
+}

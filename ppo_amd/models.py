@@ -148,6 +148,16 @@ def _custom_linear(fin, fout, scale=1.0, bias=True):
     return m.weight.data, (m.bias.data if bias else None)
 
 
+def _custom_conv(cin, cout, kernel, stride, scale=1.0):
+    """rl/tensor_utilities.py:69-94 CustomConv2d(weight_init='orthogonal'): nn.Conv2d init (its draws are consumed),
+    zero bias, then an orthogonal weight."""
+    m = torch.nn.Conv2d(cin, cout, kernel_size=(kernel, kernel), stride=(stride, stride))
+    with torch.no_grad():
+        m.bias.data *= 0
+        torch.nn.init.orthogonal_(m.weight.data, gain=scale)
+    return m.weight.data, m.bias.data
+
+
 class ImpalaSpec:
     """Static geometry of the IMPALA encoder (rl/models.py:54-99, rl/impala.py:85-123)."""
     kind = "impala"
@@ -167,6 +177,30 @@ class ImpalaSpec:
         self.flat = c * h * w
 
 
+class NatureSpec:
+    """Static geometry of the Nature-CNN encoder (rl/models.py:101-145): conv 8x8 stride 4, conv 4x4 stride 2, conv 3x3
+    stride 1, no padding, base_channels / 2x / 2x channels, a ReLU behind each, then a linear layer to hidden_units."""
+    kind = "nature"
+
+    def __init__(self, input_dims, hidden_units=512, base_channels=32):
+        if len(input_dims) != 3:
+            raise ValueError(f"the nature encoder takes [C, H, W] observations, got input_dims={input_dims}")
+        c, h, w = (int(d) for d in input_dims)
+        self.input_dims = (c, h, w)
+        self.hidden_units = hidden_units
+        self.base_channels = base_channels
+        self.layers = []  # (name, cin, cout, kernel, stride, h_in, w_in, h_out, w_out)
+        for name, cout, k, s in (("conv1", base_channels, 8, 4), ("conv2", 2 * base_channels, 4, 2),
+                                 ("conv3", 2 * base_channels, 3, 1)):
+            if h < k or w < k:
+                raise ValueError(f"input_dims={tuple(input_dims)} is too small for the nature encoder ({name}: {k}x{k} on {h}x{w})")
+            ho, wo = (h - k) // s + 1, (w - k) // s + 1
+            self.layers.append((name, c, cout, k, s, h, w, ho, wo))
+            c, h, w = cout, ho, wo
+        self.out_shape = (c, h, w)
+        self.flat = c * h * w
+
+
 class MLPSpec:
     """StandardMLP (rl/models.py:148-169): fc1 -> tanh -> fc2 on a flat float observation."""
     kind = "mlp"
@@ -181,8 +215,16 @@ class MLPSpec:
 
 def init_encoder_parameters(spec):
     """Encoder parameters as CPU tensors, drawn from torch's global CPU generator in the reference's
-    construction order (impala: rl/models.py:73-84, rl/impala.py:60-62, 96-100; mlp: rl/models.py:157-161)."""
+    construction order (impala: rl/models.py:73-84, rl/impala.py:60-62, 96-100; mlp: rl/models.py:157-161;
+    nature: rl/models.py:114-125)."""
     init = OrderedDict()
+    if spec.kind == "nature":
+        for name, cin, cout, k, s, *_r in spec.layers:
+            w, b = _custom_conv(cin, cout, k, s, scale=1.414)
+            init[f"encoder.{name}.weight"], init[f"encoder.{name}.bias"] = w, b
+        w, b = _custom_linear(spec.flat, spec.hidden_units, scale=1.414)
+        init["encoder.fc.weight"], init["encoder.fc.bias"] = w, b
+        return init
     if spec.kind == "mlp":
         w, b = _custom_linear(spec.in_features, spec.hidden_units, scale=torch.nn.init.calculate_gain("tanh"))
         init["encoder.fc1.weight"], init["encoder.fc1.bias"] = w, b
@@ -335,7 +377,9 @@ class ObsNormalizer:
 class DualHeadNet:
     """One encoder + policy / value / advantage (/ TVF) heads (reference: rl/models.py:304-508), HIP-backed.
 
-    Encoders: ``impala`` (3x3 conv stacks, uint8 or float images) and ``mlp`` (flat float observations);
+    Encoders: ``impala`` (3x3 conv stacks, uint8 or float images), ``nature`` (three strided convolutions and a linear
+    layer, uint8 or float images; op-by-op launches in exact float32 whatever `precision`) and ``mlp`` (flat float
+    observations);
     encoder activation ``relu`` (fused into the head GEMM's operand load) or ``tanh``.  All heads are ONE
     [nh, hidden] matrix so a forward is one GEMM: columns [policy nA | value VH | advantage nA | tvf K*VH].
     """
@@ -347,8 +391,8 @@ class DualHeadNet:
         encoder = encoder.lower()
         if precision not in ("low", "medium", "high"):
             raise ValueError(f"Invalid precision mode {precision}")
-        if encoder not in ("impala", "mlp"):
-            raise NotImplementedError(f"encoder '{encoder}' has no HIP path (impala | mlp)")
+        if encoder not in ("impala", "mlp", "nature"):
+            raise NotImplementedError(f"encoder '{encoder}' has no HIP path (impala | nature | mlp)")
         if activation_fn not in ("relu", "tanh"):
             raise ValueError(f"Invalid activation function {activation_fn}")
         _lib.require_gpu()
@@ -360,6 +404,11 @@ class DualHeadNet:
             self.device = torch.device("cuda", torch.cuda.current_device())
         if encoder == "impala":
             self.spec = ImpalaSpec(input_dims, hidden_units=hidden_units, **encoder_args)
+        elif encoder == "nature":
+            self.spec = NatureSpec(input_dims, hidden_units=hidden_units, **encoder_args)
+            for _name, cin, cout, k, s, h, w, _ho, _wo in self.spec.layers:
+                if not self.lib.ppo_conv2d_strided_supported(cin, cout, k, k, s, h, w):
+                    raise _lib.PpoAmdError(f"no strided-convolution kernel for {cin}->{cout} {k}x{k}/{s} on {h}x{w}")
         else:
             self.spec = MLPSpec(input_dims, hidden_units=hidden_units, **encoder_args)
         self.encoder_kind = encoder
@@ -768,6 +817,7 @@ class DualHeadNet:
                 self._call("ppo_obs_normalize_f32", _p(x), 1 if x.dtype == torch.uint8 else 0, _p(self.obs_norm.mu),
                            _p(self.obs_norm.std), self.obs_norm.norm_eps, _p(x_in), x.shape[0], self.obs_norm.F)
             acts = (self._encode_mlp(x_in, train, tag) if self.encoder_kind == "mlp"
+                    else self._encode_nature(x_in, train, tag) if self.encoder_kind == "nature"
                     else self._encode_impala(x_in, train, tag))
             if self.encoder_activation_fn == "tanh" and "heads" not in acts:
                 h = acts["h"]
@@ -800,6 +850,48 @@ class DualHeadNet:
         h = self._buf(f"{tag}h", (B, sp.hidden_units))
         self._linear(a1, sp.hidden_units, "encoder.fc2", h, tag=tag)
         return {"x": x, "a1": a1, "h": h}
+
+    def _encode_nature(self, x, train, tag):
+        """NatureCNN.forward (rl/models.py:130-145), one launch per layer: three strided convolutions with the ReLU in
+        their stores, then the linear layer - with the heads (and the action step or the PPO loss) in the same call when
+        the encoder activation is relu, as behind the IMPALA encoder."""
+        sp, B = self.spec, x.shape[0]
+        acts = {"x": x}
+        cur, mode = x, (IN_U8 if x.dtype == torch.uint8 else IN_NONE)
+        for name, cin, cout, k, s, h, w, ho, wo in sp.layers:
+            y = self._buf(f"{tag}{name}", (B, cout, ho, wo))
+            self._call("ppo_conv2d_strided_forward_f32", _p(cur), mode, _p(self.params[f"encoder.{name}.weight"]),
+                       _p(self.params[f"encoder.{name}.bias"]), _p(y), 1, B, cin, h, w, cout, k, k, s)
+            acts[name] = y
+            cur, mode = y, IN_NONE
+        flat = cur.view(B, sp.flat)  # conv3's output, already through its ReLU
+        h = self._buf(f"{tag}h", (B, sp.hidden_units))
+        if self.encoder_activation_fn == "relu":
+            o = self._buf(f"{tag}heads", (B, self.nh))
+            ws_bytes = self.lib.ppo_gemm_workspace_bytes(B, sp.hidden_units, sp.flat)
+            ws = self._ws("gemm_ws" + tag, ws_bytes)
+            args = (_p(flat), 0, _p(self.params["encoder.fc.weight"]), _p(self.params["encoder.fc.bias"]), _p(self.w_heads),
+                    _p(self.b_heads), 1, _p(h), _p(o), B, sp.flat, sp.hidden_units, self.nh, _p(ws), ws_bytes)
+            if train and self.loss_tail is not None:
+                tail, self.loss_tail = self.loss_tail, None
+                self._call("ppo_dense_heads_loss_forward_f32", *args, *tail)
+            elif self.act_tail is not None and not train:
+                # the recorded launch list keeps the plain form; its replay adds the tail of its own env step (see encode)
+                tail, self.act_tail = self.act_tail, None
+                rec, self._rec = self._rec, None
+                try:
+                    self._call("ppo_dense_heads_act_forward_f32", *args, *tail)
+                finally:
+                    self._rec = rec
+                if rec is not None:
+                    rec.append((self.lib.ppo_dense_heads_forward_f32, "ppo_dense_heads_forward_f32", args))
+            else:
+                self._call("ppo_dense_heads_forward_f32", *args)
+            acts["heads"] = o
+        else:
+            self._linear(flat, sp.flat, "encoder.fc", h, tag=tag)
+        acts["flat"], acts["h"] = flat, h
+        return acts
 
     def _stack_full_ptrs(self, si, cin, cout, h, w):
         """Host arrays of the five packed-weight / bias pointers (firstconv + the four block convolutions) of stack
@@ -1155,6 +1247,8 @@ class DualHeadNet:
             self._call("ppo_tanh_backward_f32", _p(dh), _p(hin), _p(dh), dh.numel())
         if self.encoder_kind == "mlp":
             self._backward_mlp(acts, dh)
+        elif self.encoder_kind == "nature":
+            self._backward_nature(acts, dh)
         else:
             self._backward_impala(acts, dh)
 
@@ -1165,6 +1259,34 @@ class DualHeadNet:
         self._linear_backward(acts["a1"], H, "encoder.fc2", dh, da1)
         self._call("ppo_tanh_backward_f32", _p(da1), _p(acts["a1"]), _p(da1), da1.numel())
         self._linear_backward(acts["x"], sp.in_features, "encoder.fc1", da1, None)
+
+    def _backward_nature(self, acts, dh):
+        """Backward through the Nature encoder, one launch per gradient: the linear layer (its data gradient gated by
+        conv3's output, i.e. already through conv3's ReLU), then weight and data gradients of conv3 and conv2 and the
+        weight gradient of conv1 - nothing back-propagates into the observations.  Each strided-convolution launch
+        takes the gradient w.r.t. its layer's post-ReLU output and gates it by that output itself."""
+        sp = self.spec
+        B = dh.shape[0]
+        x, flat = acts["x"], acts["flat"]
+        g = self._buf("ng_conv3", tuple(acts["conv3"].shape))
+        self._linear_backward(flat, sp.flat, "encoder.fc", dh, g.view(B, sp.flat), mask=flat)
+        gate = None  # conv3's gate is in g already
+        for li in (2, 1, 0):
+            name, cin, cout, k, s, h, w, _ho, _wo = sp.layers[li]
+            src = acts[sp.layers[li - 1][0]] if li else x
+            mode = IN_U8 if src.dtype == torch.uint8 else IN_NONE
+            geom = (B, cin, h, w, cout, k, k, s)
+            nbytes = int(self.lib.ppo_conv2d_strided_wgrad_workspace_bytes(*geom))
+            ws = self._ws("nwgrad_ws_" + name, nbytes)
+            self._call("ppo_conv2d_strided_backward_weight_f32", _p(src), mode, _p(g), _p(gate),
+                       _p(self.grads[f"encoder.{name}.weight"]), _p(self.grads[f"encoder.{name}.bias"]), _p(ws), nbytes, *geom)
+            if li:
+                gx = self._buf("ng_" + sp.layers[li - 1][0], tuple(src.shape))
+                self._call("ppo_conv2d_strided_backward_data_f32", _p(g), _p(gate), _p(self.params[f"encoder.{name}.weight"]),
+                           _p(gx), *geom)
+                g, gate = gx, src
+        if self.grad_ready_hook is not None:
+            self.grad_ready_hook(torch.cuda.current_stream())
 
     def _backward_impala(self, acts, dh):
         """Backward through the encoder.  The weight gradients run on a second stream: a layer's wgrad and its
@@ -1433,7 +1555,8 @@ class DualHeadNet:
     def takes_obs_index(self, obs) -> bool:
         """Whether a training minibatch can read its observations out of the whole batch through the permutation
         (ppo_conv3x3_pool_forward_packed_indexed_f32 + the indexed first-layer weight gradient) instead of from a
-        gathered copy: uint8 images into the fused first convolution + max-pool, the pooled-gradient weight-gradient form."""
+        gathered copy: uint8 images into the fused first convolution + max-pool, the pooled-gradient weight-gradient form.
+        IMPALA only: the nature and mlp op-by-op paths take the gathered minibatch."""
         if self.encoder_kind != "impala" or obs.dtype != torch.uint8 or self.obs_norm is not None or not GATHER_IN_CONV:
             return False
         cin, cout, h, w, _ho, _wo = self.spec.stacks[0]
