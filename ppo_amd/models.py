@@ -27,19 +27,14 @@ _ALIGN = 4  # floats: every parameter starts on a 16-byte boundary
 # bit i set: stack i runs its first convolution fused with the max-pool (bit-identical either way; the choice is
 # a measured one)
 FUSE_POOL_STACKS = int(os.environ.get("PPO_AMD_FUSE_POOL", "7"))
-# weight-gradient kernels on a second stream, overlapping the backward-data chain (0 = one stream).  It paid while single
-# weight-gradient launches left the chip half empty (round 1: -4 %); with the batched, one-wave launches every kernel
-# fills the chip on its own and the second stream costs ~1 % (83.1 k vs 82.3 k env-steps/s), so the default is one stream.
-WGRAD_SIDE_STREAM = int(os.environ.get("PPO_AMD_WGRAD_STREAM", "0"))
-# the slab reductions of all convolution layers in one launch at the end of the backward pass (0 = one per layer)
-WGRAD_BATCH_REDUCE = int(os.environ.get("PPO_AMD_WGRAD_BATCH_REDUCE", "1"))
-# The four block convolutions of a stack share a geometry: their weight gradients go out as ONE launch (4 x the
-# workgroups, one ramp and one tail) once the stack's backward-data pass is through.  Needs WGRAD_BATCH_REDUCE.
+# (Every convolution's weight gradient is formed as slabs in a workspace of its own, and one launch at the end of the
+# backward pass reduces the slabs of all layers.)  The four block convolutions of a stack share a geometry: their weight
+# gradients go out as ONE launch (4 x the workgroups, one ramp and one tail) once the stack's backward-data pass is through.
 WGRAD_BATCH_LAUNCH = int(os.environ.get("PPO_AMD_WGRAD_BATCH_LAUNCH", "1"))
 # The first stack's max-pool backward is folded into its first convolution's weight-gradient kernel (the only reader of
-# that 84x84 gradient map: nothing back-propagates into the observations).  Needs WGRAD_BATCH_REDUCE.  Measured: the
-# max-pool backward launch (37 us) goes, the weight-gradient kernel grows by ~20 us (it gathers (argmax, g) pairs
-# instead of streaming the map in by LDS-DMA): -15 us per step net and a 115 MB tensor less.
+# that 84x84 gradient map: nothing back-propagates into the observations).  Measured: the max-pool backward launch
+# (37 us) goes, the weight-gradient kernel grows by ~20 us (it gathers (argmax, g) pairs instead of streaming the map in
+# by LDS-DMA): -15 us per step net and a 115 MB tensor less.
 WGRAD_POOLED_DY = int(os.environ.get("PPO_AMD_WGRAD_POOLED_DY", "1"))
 # a stack's first convolution whose geometry equals the PREVIOUS stack's block convolutions (32 -> 32 at 21x21 for the 84x84
 # net) has its weight gradient formed by that stack's batched launch, as a fifth problem read without the ReLU
@@ -48,11 +43,10 @@ WGRAD_RIDE = int(os.environ.get("PPO_AMD_WGRAD_RIDE", "1"))
 # --precision=medium|low only: weight gradients of the 16- and 32-channel float layers as split-bf16 products too
 # (csrc/wgrad_bf16x3.hip; 0 keeps them on the exact float32 kernel while the residual blocks stay split).
 SPLIT_WGRAD = int(os.environ.get("PPO_AMD_SPLIT_WGRAD", "1"))
-# likewise the stack-first convolutions (forward: split convolution + the max-pool launch instead of the fused float32
-# conv + pool kernel; backward-data): csrc/conv_bf16x3.hip
+# likewise the stack-first convolutions (forward: split convolution, with the max-pool inside the launch where that
+# geometry has a kernel and as a launch of its own elsewhere, instead of the fused float32 conv + pool kernel;
+# backward-data): csrc/conv_bf16x3.hip
 SPLIT_CONV = int(os.environ.get("PPO_AMD_SPLIT_CONV", "1"))
-SPLIT_CONV_POOL = int(os.environ.get("PPO_AMD_SPLIT_CONV_POOL", "1"))  # ... with the max-pool inside the launch
-SPLIT_SIGNS = int(os.environ.get("PPO_AMD_SPLIT_SIGNS", "1"))  # the split backward chains read 1-bit gates written by the forward
 # convolutions read their MFMA A operand from a pre-packed copy of the weights, refreshed by one launch after every
 # optimiser step (0 = every kernel stages the raw tensor through LDS itself); bit-identical either way
 PACKED_WEIGHTS = int(os.environ.get("PPO_AMD_PACKED_WEIGHTS", "1"))
@@ -79,22 +73,21 @@ FUSE_STACK_CHAIN = int(os.environ.get("PPO_AMD_FUSE_STACK_CHAIN", "1"))
 # under `net.allow_chain_split` (the Runner's pipelined rollout sets it, and checks) takes the split launch: evaluation,
 # greedy and generic-rollout forwards, whose callers never look at the error word, keep the one-workgroup launch.
 CHAIN_SPLIT = int(os.environ.get("PPO_AMD_CHAIN_SPLIT", "1"))
-CHAIN_SPLIT_MAX_BATCH = int(os.environ.get("PPO_AMD_CHAIN_SPLIT_MAX_BATCH", "128"))
+CHAIN_SPLIT_MAX_BATCH = 128
 # ... and its backward-data pass (blocks + max-pool backward + transposed first convolution) likewise.  Off by default:
-# bit-identical, but 1.445 ms per 256-sample step against 1.395 without it — it holds a whole CU's LDS, so the
-# weight-gradient kernels on the side stream get nothing to overlap with for its duration, and releases the five
-# gradients they wait for only at its end.
+# bit-identical, but 1.445 ms per 256-sample step against 1.395 without it (measured while the weight-gradient kernels
+# still ran on a second stream: it holds a whole CU's LDS, so they got nothing to overlap with for its duration, and it
+# releases the five gradients they wait for only at its end).
 FUSE_STACK_FULL_BWD = int(os.environ.get("PPO_AMD_FUSE_STACK_FULL_BWD", "0"))
 # ... and the same for their backward-data chain, as a bit mask over the stacks (per 256-sample step, same box:
 # 1.476 ms with mask 0, 1.450 with 4 (11x11), 1.404 with 2 (21x21), 1.408 with 6).
 FUSE_STACK_TAIL_BWD = int(os.environ.get("PPO_AMD_FUSE_STACK_TAIL_BWD", "7"))
 # The 16-channel stack's blocks (42x42 / 32x32: the map fills most of a CU's LDS) as the in-place, row-shifted form of the
-# same kernel family (csrc/stack_fused.hip stack_shift_kernel); 0 = four convolution launches.  One 16-wave workgroup per
+# same kernel family (csrc/stack_fused.hip stack_shift_kernel) instead of four convolution launches.  One 16-wave workgroup per
 # image and per CU, two wave groups half a band apart (one in its K loop while the other runs its epilogue): measured at
 # batch 256 forward 0.398 -> 0.393 ms, training step 1.219 -> 1.186 ms with the backward-data form too (bit 0 of the mask
 # above).  At 128 images (a rollout group) it leaves half the chip idle (0.296 -> 0.325 ms), so batches below
 # FUSE_STACK16_MIN_BATCH keep the four launches.  Same bits either way.
-FUSE_STACK16 = int(os.environ.get("PPO_AMD_FUSE_STACK16", "1"))
 FUSE_STACK16_MIN_BATCH = int(os.environ.get("PPO_AMD_FUSE_STACK16_MIN_BATCH", "192"))
 # Below that batch an inference forward runs each 16-channel residual block as one launch (csrc/conv3x3_block.hip: band by
 # band, the intermediate map in LDS) instead of two convolution launches: a 128-image group is launch-cost-bound there.
@@ -104,9 +97,6 @@ FUSE_BLOCK = int(os.environ.get("PPO_AMD_FUSE_BLOCK", "1"))
 # statistics; Adam) instead of ~14 launches of 8 - 20 us each.  0 = the op-by-op path (same arithmetic per element up to
 # float32 summation order; tests/test_variants_gpu.py runs both against the reference's fixtures).
 FUSE_MLP = int(os.environ.get("PPO_AMD_FUSE_MLP", "1"))
-# the discrete PPO loss runs on the finished head row inside the training forward's dense + heads launch
-# (ppo_dense_heads_loss_forward_f32): bit-identical, one latency-bound launch less per minibatch
-FUSE_LOSS = int(os.environ.get("PPO_AMD_FUSE_LOSS", "1"))
 # uint8 image minibatches are read out of the whole rollout batch through the permutation by the first convolution (and by
 # its weight gradient) instead of being gathered into a second buffer by a launch of its own (0 = gather first)
 GATHER_IN_CONV = int(os.environ.get("PPO_AMD_GATHER_IN_CONV", "1"))
@@ -741,23 +731,15 @@ class DualHeadNet:
         self._call("ppo_gemm_f32", _p(x), k, 1, relu_x, _p(w), 1, k, 0, _p(self.params[wname + ".bias"]), None,
                    _p(out), n, B, n, k, _p(ws), ws_bytes)
 
-    def _linear_backward(self, x, k, wname, dy, dx, relu_x=0, mask=None, acc=0, side=None):
-        """dW = dy^T @ f(x), db = colsum(dy), dx = (dy @ W) [* (mask > 0)]  (dx nullable).  With `side` (a stream
-        that already waits for dy) the two parameter gradients go there and only dx stays on the current stream."""
+    def _linear_backward(self, x, k, wname, dy, dx, relu_x=0, mask=None, acc=0, bias_done=False):
+        """dW = dy^T @ f(x), db = colsum(dy), dx = (dy @ W) [* (mask > 0)]  (dx nullable).  `bias_done`: an earlier
+        launch has written db already."""
         w = self.params[wname + ".weight"]
         B, n = dy.shape[0], w.shape[0]
-
-        def param_grads():
-            self._call("ppo_gemm_f32", _p(dy), 1, n, 0, _p(x), k, 1, relu_x, None, None,
-                       _p(self.grads[wname + ".weight"]), k, n, k, B, None, 0)
-            if not (wname == "encoder.dense" and getattr(self, "_dense_bias_done", False)):  # heads backward made it
-                self._call("ppo_colsum_f32", _p(dy), B, n, n, _p(self.grads[wname + ".bias"]), acc)
-
-        if side is None:
-            param_grads()
-        else:
-            with torch.cuda.stream(side):
-                param_grads()
+        self._call("ppo_gemm_f32", _p(dy), 1, n, 0, _p(x), k, 1, relu_x, None, None,
+                   _p(self.grads[wname + ".weight"]), k, n, k, B, None, 0)
+        if not bias_done:
+            self._call("ppo_colsum_f32", _p(dy), B, n, n, _p(self.grads[wname + ".bias"]), acc)
         if dx is not None:
             self._call("ppo_gemm_f32", _p(dy), n, 1, 0, _p(w), k, 1, 0, None, _p(mask), _p(dx), k, B, k, n, None, 0)
 
@@ -916,7 +898,7 @@ class DualHeadNet:
         kernel, or None when it does not apply.  The arrays are cached: packed buffers and parameter views keep
         their addresses for the life of the net."""
         if not FUSE_STACK_TAIL or self.spec.n_block != 2 or not self.lib.ppo_impala_stack_tail_supported(cout, ho, wo) \
-                or (cout == 16 and (not FUSE_STACK16 or batch < FUSE_STACK16_MIN_BATCH)):
+                or (cout == 16 and batch < FUSE_STACK16_MIN_BATCH):
             return None
         cached = self._tail_ptrs.get(si)
         if cached is None:
@@ -1030,8 +1012,9 @@ class DualHeadNet:
                 cur, cur_mode = q1, IN_NONE
                 continue
             if self.split_bf16 and (wname, 0) in self._pk16 and cur_mode != IN_U8 and cur.dtype == torch.float32:
-                # --precision=low|medium: the stack-first convolution as split-bf16 products, then the max-pool launch
-                if SPLIT_CONV_POOL and self.lib.ppo_conv3x3_pool_bf16x3_supported(cin, cout, h, w):
+                # --precision=low|medium: the stack-first convolution as split-bf16 products, with the max-pool inside the
+                # launch or behind it
+                if self.lib.ppo_conv3x3_pool_bf16x3_supported(cin, cout, h, w):
                     self._call("ppo_conv3x3_pool_bf16x3", _p(cur), int(cur_mode == IN_RELU), _p(self._pk16[(wname, 0)]),
                                _p(self.params[wname + ".bias"]), _p(p), _p(idx), B, cin, cout, h, w)
                 else:
@@ -1060,7 +1043,7 @@ class DualHeadNet:
                 # --precision=low|medium: this stack's residual blocks as the split-bf16 launch
                 names = [f"{tag}a{si}_0", f"{tag}q{si}_0", f"{tag}a{si}_1", f"{tag}q{si}_1"]
                 a0, q0, a1, q1 = (self._buf(nm, (B, cout, ho, wo)) for nm in names)
-                if train and SPLIT_SIGNS and cout == 16:  # (measured: 82 -> 61 us for the 16-channel backward chain; nothing at 32 channels)
+                if train and cout == 16:  # (measured: 82 -> 61 us for the 16-channel backward chain; nothing at 32 channels)
                     # the backward chain's gates as sign maps (1 byte per 4 elements instead of 4 float32 maps read for a sign)
                     sg = [self._buf(f"{tag}sg{si}_{k}", (B, cout // 4, ho, wo), torch.uint8) for k in range(4)]
                     acts[f"signs{si}"] = (ctypes.c_void_p * 4)(*[t.data_ptr() for t in sg])
@@ -1214,33 +1197,20 @@ class DualHeadNet:
         h = acts["h"]
         relu = self.encoder_activation_fn == "relu"
         hin = h if relu else acts["hact"]
-        # heads: dW = dheads^T @ act(h); db = colsum(dheads); dh = (dheads @ W) * act'(h).  The parameter gradients
-        # (small, latency-bound launches) go to the side stream of the convolution weight gradients; the main stream
-        # carries only the dX chain.
-        main = torch.cuda.current_stream()
-        side = self._wgrad_side_stream() if (WGRAD_SIDE_STREAM and self.encoder_kind == "impala") else None
-
+        # heads: dW = dheads^T @ act(h); db = colsum(dheads); dh = (dheads @ W) * act'(h)
         dh = self._buf("dh", (B, H))
         # one launch: dh, the heads' weight / bias gradients and - when dh is final (relu) - the dense layer's bias
         # gradient, which is the column sum of dh
-        self._dense_bias_done = bool(relu and self.encoder_kind == "impala" and self.nh <= 16)
+        dense_bias_done = bool(relu and self.encoder_kind == "impala" and self.nh <= 16)
         if self.nh <= 16:
             self._call("ppo_heads_backward_f32", _p(dheads), _p(hin), 1 if relu else 0, _p(h) if relu else None, _p(self.w_heads),
                        _p(dh), _p(self.g_w_heads), _p(self.g_b_heads) if self.head_bias else None,
-                       _p(self.grads["encoder.dense.bias"]) if self._dense_bias_done else None, B, H, self.nh)
+                       _p(self.grads["encoder.dense.bias"]) if dense_bias_done else None, B, H, self.nh)
         else:
-            def head_param_grads():
-                self._call("ppo_gemm_f32", _p(dheads), 1, self.nh, 0, _p(hin), H, 1, 1 if relu else 0, None, None,
-                           _p(self.g_w_heads), H, self.nh, H, B, None, 0)
-                if self.head_bias:
-                    self._call("ppo_colsum_f32", _p(dheads), B, self.nh, self.nh, _p(self.g_b_heads), 0)
-
-            if side is None:
-                head_param_grads()
-            else:
-                side.wait_stream(main)  # dheads (and the forward activations) are complete
-                with torch.cuda.stream(side):
-                    head_param_grads()
+            self._call("ppo_gemm_f32", _p(dheads), 1, self.nh, 0, _p(hin), H, 1, 1 if relu else 0, None, None,
+                       _p(self.g_w_heads), H, self.nh, H, B, None, 0)
+            if self.head_bias:
+                self._call("ppo_colsum_f32", _p(dheads), B, self.nh, self.nh, _p(self.g_b_heads), 0)
             self._call("ppo_gemm_f32", _p(dheads), self.nh, 1, 0, _p(self.w_heads), H, 1, 0, None, _p(h) if relu else None,
                        _p(dh), H, B, H, self.nh, None, 0)
         if not relu:
@@ -1250,7 +1220,7 @@ class DualHeadNet:
         elif self.encoder_kind == "nature":
             self._backward_nature(acts, dh)
         else:
-            self._backward_impala(acts, dh)
+            self._backward_impala(acts, dh, dense_bias_done)
 
     def _backward_mlp(self, acts, dh):
         sp = self.spec
@@ -1288,73 +1258,59 @@ class DualHeadNet:
         if self.grad_ready_hook is not None:
             self.grad_ready_hook(torch.cuda.current_stream())
 
-    def _backward_impala(self, acts, dh):
-        """Backward through the encoder.  The weight gradients run on a second stream: a layer's wgrad and its
-        backward-data only share inputs, so the wgrad's ramp-up / tail overlaps the next backward-data kernel
-        instead of leaving the chip half empty (every kernel here is a persistent grid with a few-microsecond
-        prologue and a ragged tail).  Every gradient tensor has its own buffer within a pass, so the two
-        streams never reuse memory the other still reads; the main stream joins the side stream at the end."""
+    def _backward_impala(self, acts, dh, dense_bias_done=False):
+        """Backward through the encoder, every launch on the current stream: the dense layer, then stack by stack from
+        the last one the backward-data chain of the blocks (one fused launch where the geometry has a kernel), max-pool
+        backward and the transposed first convolution.  Weight gradients are formed as slabs, each layer in a workspace
+        of its own - the block convolutions of a stack in one launch behind that stack's backward-data chain - and one
+        launch at the end of the pass reduces the slabs of all layers into self.grad.  Every gradient tensor has its own
+        buffer within a pass.  `dense_bias_done`: the heads launch wrote encoder.dense.bias's gradient already."""
         sp, lib = self.spec, self.lib
         B, H = dh.shape
         flat = acts["flat"]
         # dense: dW = dh^T @ relu(flat); db = colsum(dh); dflat = (dh @ W) * (flat > 0)
         c_last, h_last, w_last = sp.out_shape
         g = self._buf(f"g{len(sp.stacks) - 1}_top", (B, c_last, h_last, w_last))
-        main = torch.cuda.current_stream()
-        side = self._wgrad_side_stream() if WGRAD_SIDE_STREAM else None
-        if side is not None:
-            side.wait_stream(main)  # dh is complete
-        self._linear_backward(flat, sp.flat, "encoder.dense", dh, g, relu_x=1, mask=flat, side=side)
+        self._linear_backward(flat, sp.flat, "encoder.dense", dh, g, relu_x=1, mask=flat, bias_done=dense_bias_done)
         if self.grad_ready_hook is not None:
             # dense + head gradients (the tail of the flat buffer from `early_grad_offset` on) are final once the
             # launches queued so far on this stream have run: a data-parallel reducer ships them under the rest
-            self.grad_ready_hook(side if side is not None else main)
-
-        n_wgrad = [0]
+            self.grad_ready_hook(torch.cuda.current_stream())
 
         jobs = []  # deferred slab reductions: one launch for all layers at the end of the pass
 
         def split_wgrad(mode, cin, cout, hh, ww):
             """--precision=medium|low: this layer's weight gradient as split-bf16 products (csrc/wgrad_bf16x3.hip)."""
-            return self.split_bf16 and SPLIT_WGRAD and WGRAD_BATCH_REDUCE and mode in (IN_NONE, IN_RELU) \
+            return self.split_bf16 and SPLIT_WGRAD and mode in (IN_NONE, IN_RELU) \
                 and lib.ppo_conv3x3_backward_weight_bf16x3_supported(cin, cout, hh, ww)
+
+        def slab_launch(args_, n_slabs, layers, cin, cout):
+            """One slab launch for layers = [(wname, its workspace)]; the kernel reports the slab count through n_slabs."""
+            self._call(*args_)
+            for wname, ws in layers:
+                jobs.append(_lib.WgradJob(_p(ws), _p(self.grads[wname + ".weight"]), _p(self.grads[wname + ".bias"]),
+                                          n_slabs.value, cin, cout, 0))
 
         def wgrad(x, mode, dy, wname, n, cin, cout, hh, ww, argmax=None):
             """argmax given: dy is the POOLED gradient and the kernel forms max-pool backward itself."""
             nbytes = lib.ppo_conv3x3_wgrad_workspace_bytes(cin, cout)
-            if WGRAD_BATCH_REDUCE:
-                ws = self._ws("wgrad_ws_" + wname, nbytes)  # per layer: the slabs live until the batched reduction
-                n_slabs = ctypes.c_int(0)
-                if argmax is not None and acts.get("in0_index") is not None and wname == "encoder.stacks.0.firstconv":
-                    args_ = ("ppo_conv3x3_backward_weight_slabs_pooled_indexed_f32", _p(x), _p(acts["in0_index"]), mode, _p(dy),
-                             _p(argmax), _p(ws), nbytes, n, cin, cout, hh, ww, ctypes.addressof(n_slabs))
-                elif argmax is not None:
-                    args_ = ("ppo_conv3x3_backward_weight_slabs_pooled_f32", _p(x), mode, _p(dy), _p(argmax), _p(ws),
-                             nbytes, n, cin, cout, hh, ww, ctypes.addressof(n_slabs))
-                elif split_wgrad(mode, cin, cout, hh, ww):
-                    keep = ((ctypes.c_void_p * 1)(x.data_ptr()), (ctypes.c_int * 1)(int(mode == IN_RELU)),
-                            (ctypes.c_void_p * 1)(dy.data_ptr()), (ctypes.c_void_p * 1)(ws.data_ptr()))
-                    args_ = ("ppo_conv3x3_backward_weight_slabs_batch_bf16x3", keep[0], keep[1], keep[2], keep[3], nbytes, 1, n,
-                             cin, cout, hh, ww, ctypes.addressof(n_slabs))
-                else:
-                    args_ = ("ppo_conv3x3_backward_weight_slabs_f32", _p(x), mode, _p(dy), _p(ws), nbytes, n, cin, cout,
-                             hh, ww, ctypes.addressof(n_slabs))
+            ws = self._ws("wgrad_ws_" + wname, nbytes)  # per layer: the slabs live until the batched reduction
+            n_slabs = ctypes.c_int(0)
+            if argmax is not None and acts.get("in0_index") is not None and wname == "encoder.stacks.0.firstconv":
+                args_ = ("ppo_conv3x3_backward_weight_slabs_pooled_indexed_f32", _p(x), _p(acts["in0_index"]), mode, _p(dy),
+                         _p(argmax), _p(ws), nbytes, n, cin, cout, hh, ww, ctypes.addressof(n_slabs))
+            elif argmax is not None:
+                args_ = ("ppo_conv3x3_backward_weight_slabs_pooled_f32", _p(x), mode, _p(dy), _p(argmax), _p(ws),
+                         nbytes, n, cin, cout, hh, ww, ctypes.addressof(n_slabs))
+            elif split_wgrad(mode, cin, cout, hh, ww):
+                keep = ((ctypes.c_void_p * 1)(x.data_ptr()), (ctypes.c_int * 1)(int(mode == IN_RELU)),
+                        (ctypes.c_void_p * 1)(dy.data_ptr()), (ctypes.c_void_p * 1)(ws.data_ptr()))
+                args_ = ("ppo_conv3x3_backward_weight_slabs_batch_bf16x3", keep[0], keep[1], keep[2], keep[3], nbytes, 1, n,
+                         cin, cout, hh, ww, ctypes.addressof(n_slabs))
             else:
-                ws = self._ws("wgrad_ws", nbytes)
-                args_ = ("ppo_conv3x3_backward_weight_f32", _p(x), mode, _p(dy), _p(self.grads[wname + ".weight"]),
-                         _p(self.grads[wname + ".bias"]), _p(ws), nbytes, n, cin, cout, hh, ww, 0)
-            if side is None:
-                self._call(*args_)
-            else:
-                ev = self._wgrad_events[n_wgrad[0]]
-                n_wgrad[0] += 1
-                ev.record(main)  # dy (and everything before it) is ready
-                side.wait_event(ev)
-                with torch.cuda.stream(side):
-                    self._call(*args_)
-            if WGRAD_BATCH_REDUCE:
-                jobs.append(_lib.WgradJob(_p(ws), _p(self.grads[wname + ".weight"]), _p(self.grads[wname + ".bias"]),
-                                          n_slabs.value, cin, cout, 0))
+                args_ = ("ppo_conv3x3_backward_weight_slabs_f32", _p(x), mode, _p(dy), _p(ws), nbytes, n, cin, cout,
+                         hh, ww, ctypes.addressof(n_slabs))
+            slab_launch(args_, n_slabs, [(wname, ws)], cin, cout)
 
         carry = []  # [(x, dy, wname, n, c, hh, ww)]: a first convolution waiting for the next batched launch of its geometry
 
@@ -1365,7 +1321,7 @@ class DualHeadNet:
 
         def wgrad_blocks(problems, n, c, hh, ww):
             """Weight gradients of a stack's block convolutions, problems = [(x, dy, wname)] (all IN_RELU, c -> c)."""
-            if not (WGRAD_BATCH_LAUNCH and WGRAD_BATCH_REDUCE) or len(problems) > 4:
+            if not WGRAD_BATCH_LAUNCH or len(problems) > 4:
                 flush_carry()
                 for x, dy, wname in problems:
                     wgrad(x, IN_RELU, dy, wname, n, c, c, hh, ww)
@@ -1392,50 +1348,29 @@ class DualHeadNet:
             else:
                 args_ = ("ppo_conv3x3_backward_weight_slabs_batch_f32", ins, IN_RELU, dys, wsp, nbytes, k, n, c, c, hh, ww,
                          ctypes.addressof(n_slabs))
-            if side is None:
-                self._call(*args_)
-            else:
-                ev = self._wgrad_events[n_wgrad[0]]
-                n_wgrad[0] += 1
-                ev.record(main)  # every dy of the stack is ready
-                side.wait_event(ev)
-                with torch.cuda.stream(side):
-                    self._call(*args_)
-            for (_x, _dy, wname), ws in zip(problems, wss):
-                jobs.append(_lib.WgradJob(_p(ws), _p(self.grads[wname + ".weight"]), _p(self.grads[wname + ".bias"]),
-                                          n_slabs.value, c, c, 0))
+            slab_launch(args_, n_slabs, [(wname, ws) for (_x, _dy, wname), ws in zip(problems, wss)], c, c)
 
         for si in reversed(range(len(sp.stacks))):
             cin, cout, hh, ww, ho, wo = sp.stacks[si]
+            # blocks + max-pool backward + transposed first convolution of the stack in one launch, ...
             full_w = self._stack_full_bwd_ptrs(si, cin, cout, hh, ww) if si > 0 else None
-            if full_w is not None:
-                # blocks + max-pool backward + transposed first convolution of the stack in one launch
-                b0, b1 = f"encoder.stacks.{si}.blocks.0", f"encoder.stacks.{si}.blocks.1"
-                p_in, a0, q0, a1 = acts[f"q{si}_0_in"], acts[f"a{si}_0"], acts[f"q{si}_1_in"], acts[f"a{si}_1"]
-                da1, g1, da0, g0 = (self._buf(nm, (B, cout, ho, wo)) for nm in
-                                    (f"g{si}_1_da", f"g{si}_1_in", f"g{si}_0_da", f"g{si}_0_in"))
-                dc = self._buf(f"g{si}_dc", (B, cout, hh, ww))
-                g_prev = self._buf(f"g{si - 1}_top", (B, cin, hh, ww))
-                masks = (ctypes.c_void_p * 4)(a1.data_ptr(), q0.data_ptr(), a0.data_ptr(), p_in.data_ptr())
-                self._call("ppo_impala_stack_full_backward_f32", _p(g), full_w, masks, _p(acts[f"idx{si}"]), _p(da1), _p(g1),
-                           _p(da0), _p(g0), _p(dc), _p(g_prev), B, cout, hh, ww)
-                wgrad_blocks([(a1, g, b1 + ".conv1"), (q0, da1, b1 + ".conv0"), (a0, g1, b0 + ".conv1"),
-                              (p_in, da0, b0 + ".conv0")], B, cout, ho, wo)
-                wgrad(acts[f"in{si}"], IN_NONE, dc, f"encoder.stacks.{si}.firstconv", B, cin, cout, hh, ww)
-                g = g_prev
-                continue
-            tail_w = self._stack_tail_bwd_ptrs(si, cout, ho, wo)
-            split = self.split_bf16 and (si, 1) in self._pk16
-            if split:
-                tail_w = True  # the gated transposed chain of this stack's blocks as the split-bf16 launch
-            if tail_w is not None:
-                # the four backward-data convolutions of the stack's blocks in one launch (csrc/stack_fused.hip)
+            # ... or the four backward-data convolutions of the stack's blocks in one launch (csrc/stack_fused.hip), ...
+            tail_w = self._stack_tail_bwd_ptrs(si, cout, ho, wo) if full_w is None else None
+            # ... which in split mode is the gated transposed chain of this stack's blocks as the split-bf16 launch
+            split = full_w is None and self.split_bf16 and (si, 1) in self._pk16
+            fused = full_w is not None or tail_w is not None or split
+            if fused:
                 b0, b1 = f"encoder.stacks.{si}.blocks.0", f"encoder.stacks.{si}.blocks.1"
                 p_in, a0, q0, a1 = acts[f"q{si}_0_in"], acts[f"a{si}_0"], acts[f"q{si}_1_in"], acts[f"a{si}_1"]
                 da1, g1, da0, g0 = (self._buf(nm, (B, cout, ho, wo)) for nm in
                                     (f"g{si}_1_da", f"g{si}_1_in", f"g{si}_0_da", f"g{si}_0_in"))
                 masks = (ctypes.c_void_p * 4)(a1.data_ptr(), q0.data_ptr(), a0.data_ptr(), p_in.data_ptr())
-                if split and acts.get(f"signs{si}") is not None:
+                if full_w is not None:
+                    dc = self._buf(f"g{si}_dc", (B, cout, hh, ww))
+                    g_prev = self._buf(f"g{si - 1}_top", (B, cin, hh, ww))
+                    self._call("ppo_impala_stack_full_backward_f32", _p(g), full_w, masks, _p(acts[f"idx{si}"]), _p(da1), _p(g1),
+                               _p(da0), _p(g0), _p(dc), _p(g_prev), B, cout, hh, ww)
+                elif split and acts.get(f"signs{si}") is not None:
                     self._call("ppo_impala_stack_tail_backward_signs_bf16x3", _p(g), _p(self._pk16[(si, 1)]), acts[f"signs{si}"],
                                _p(da1), _p(g1), _p(da0), _p(g0), B, cout, ho, wo)
                 elif split:
@@ -1446,10 +1381,14 @@ class DualHeadNet:
                                B, cout, ho, wo)
                 wgrad_blocks([(a1, g, b1 + ".conv1"), (q0, da1, b1 + ".conv0"), (a0, g1, b0 + ".conv1"),
                               (p_in, da0, b0 + ".conv0")], B, cout, ho, wo)
+                if full_w is not None:
+                    wgrad(acts[f"in{si}"], IN_NONE, dc, f"encoder.stacks.{si}.firstconv", B, cin, cout, hh, ww)
+                    g = g_prev
+                    continue
                 g = g0
-            defer = WGRAD_BATCH_LAUNCH and WGRAD_BATCH_REDUCE and sp.n_block * 2 <= 4
+            defer = WGRAD_BATCH_LAUNCH and sp.n_block * 2 <= 4
             problems = []
-            for bi in (reversed(range(sp.n_block)) if tail_w is None else ()):
+            for bi in (() if fused else reversed(range(sp.n_block))):
                 base = f"encoder.stacks.{si}.blocks.{bi}"
                 q_in, a = acts[f"q{si}_{bi}_in"], acts[f"a{si}_{bi}"]
                 # g = d loss / d (block output);  block: out = q_in + conv1(relu(conv0(relu(q_in))))
@@ -1473,14 +1412,13 @@ class DualHeadNet:
             # max-pool backward, then the stack's first convolution
             x_in = acts[f"in{si}"]
             mode = IN_NONE if si > 0 else (IN_U8 if x_in.dtype == torch.uint8 else IN_NONE)
-            if si == 0 and WGRAD_POOLED_DY and WGRAD_BATCH_REDUCE \
-                    and lib.ppo_conv3x3_backward_weight_pooled_supported(cin, cout, hh, ww):
+            if si == 0 and WGRAD_POOLED_DY and lib.ppo_conv3x3_backward_weight_pooled_supported(cin, cout, hh, ww):
                 # nothing else reads this stack's pre-pool gradient: the weight-gradient kernel forms it band by band
                 wgrad(x_in, mode, g, f"encoder.stacks.{si}.firstconv", B, cin, cout, hh, ww, argmax=acts[f"idx{si}"])
                 continue
             dc = self._buf(f"g{si}_dc", (B, cout, hh, ww))
             self._call("ppo_maxpool3x3s2_backward_f32", _p(g), _p(acts[f"idx{si}"]), _p(dc), B, cout, hh, ww)
-            if WGRAD_RIDE and WGRAD_BATCH_LAUNCH and WGRAD_BATCH_REDUCE and side is None and si > 0 and cin == cout \
+            if WGRAD_RIDE and WGRAD_BATCH_LAUNCH and si > 0 and cin == cout \
                     and mode == IN_NONE and sp.n_block == 2 and sp.stacks[si - 1][1] == cin \
                     and tuple(sp.stacks[si - 1][4:6]) == (hh, ww):
                 carry.append((x_in, dc, f"encoder.stacks.{si}.firstconv", B, cin, hh, ww))  # rides in the next stack's launch
@@ -1497,13 +1435,7 @@ class DualHeadNet:
         flush_carry()
         if jobs:
             table = (_lib.WgradJob * len(jobs))(*jobs)
-            if side is None:
-                self._call("ppo_conv3x3_wgrad_reduce_f32", ctypes.addressof(table), len(jobs))
-            else:
-                with torch.cuda.stream(side):
-                    self._call("ppo_conv3x3_wgrad_reduce_f32", ctypes.addressof(table), len(jobs))
-        if side is not None:
-            main.wait_stream(side)  # all weight gradients are in self.grad before anything reads it
+            self._call("ppo_conv3x3_wgrad_reduce_f32", ctypes.addressof(table), len(jobs))
 
     def _stack_full_bwd_ptrs(self, si, cin, cout, h, w):
         """Host array of the five backward-data packed weights of stack si in processing order (block1.conv1,
@@ -1526,7 +1458,7 @@ class DualHeadNet:
         """Host array of the four backward-data packed weights of stack si's blocks in processing order
         (block1.conv1, block1.conv0, block0.conv1, block0.conv0), or None when the fused kernel does not apply."""
         if not (FUSE_STACK_TAIL and FUSE_STACK_TAIL_BWD >> si & 1) or self.spec.n_block != 2 \
-                or not self.lib.ppo_impala_stack_tail_supported(cout, ho, wo) or (cout == 16 and not FUSE_STACK16):
+                or not self.lib.ppo_impala_stack_tail_supported(cout, ho, wo):
             return None
         cached = self._tail_ptrs.get(("bwd", si))
         if cached is None:
@@ -1544,13 +1476,6 @@ class DualHeadNet:
     def _bwd_w(self, wname):
         return self._pk.get((wname, 1), self.params[wname + ".weight"])
 
-    def _wgrad_side_stream(self):
-        if getattr(self, "_wgrad_stream", None) is None:
-            self._wgrad_stream = torch.cuda.Stream(device=self.device)
-            n = len(self.spec.stacks) * (1 + 2 * self.spec.n_block)
-            self._wgrad_events = [torch.cuda.Event() for _ in range(n)]
-        return self._wgrad_stream
-
     # ------------------------------------------------------------------ minibatch losses + optimiser
     def takes_obs_index(self, obs) -> bool:
         """Whether a training minibatch can read its observations out of the whole batch through the permutation
@@ -1561,7 +1486,7 @@ class DualHeadNet:
             return False
         cin, cout, h, w, _ho, _wo = self.spec.stacks[0]
         return bool(FUSE_POOL_STACKS & 1) and self._pk.get(("encoder.stacks.0.firstconv", 0)) is not None \
-            and bool(WGRAD_POOLED_DY and WGRAD_BATCH_REDUCE) \
+            and bool(WGRAD_POOLED_DY) \
             and bool(self.lib.ppo_conv3x3_backward_weight_pooled_supported(cin, cout, h, w))
 
     @staticmethod
@@ -1620,11 +1545,12 @@ class DualHeadNet:
         loss_args = (self.n_actions, vh, _p(actions), _p(old_log_pac), _p(old_log_policy), _p(advantages), _p(returns),
                      float(eps_clip), float(ent_coef), float(vf_coef), float(loss_scale) / B,
                      _p(self._buf("dheads", (B, self.nh))), _p(stats), _p(index))
-        # the loss rides on the dense + heads launch of the training forward where that launch exists (IMPALA, relu)
-        self.loss_tail = loss_args if FUSE_LOSS else None
+        # the loss rides on the dense + heads launch of the training forward where that launch exists (IMPALA, relu:
+        # ppo_dense_heads_loss_forward_f32, bit-identical, one latency-bound launch less per minibatch)
+        self.loss_tail = loss_args
         try:
             acts, o, B, dheads = self._train_forward(prev_state, index, obs_indexed)
-            fused = FUSE_LOSS and self.loss_tail is None
+            fused = self.loss_tail is None
         finally:
             self.loss_tail = None
         if not fused:

@@ -21,7 +21,6 @@ What changed relative to the reference, and why (MI355X-first):
 """
 import copy
 import math
-import os
 
 import numpy as np
 import torch
@@ -32,16 +31,9 @@ from .models import AdamState
 from .returns import calculate_bootstrapped_returns
 
 
-# 1: replay the rollout forward of each env group as a hipGraph.  Measured on MI355X / ROCm 7.2: 0.794 ms per
-# env step with graphs vs 0.731 ms eager (graph launches of ~25 kernel nodes cost more than the ctypes calls
-# they replace and overlap less across the two group streams), so the default is eager.
-ROLLOUT_GRAPH = int(os.environ.get("PPO_AMD_ROLLOUT_GRAPH", "0"))
 # the synthetic env uploads a group's observations in this many pieces, each as soon as it has been generated (1: one
 # copy after the whole group has been stepped).  Measured: 0.491 / 0.474 / 0.487 / 0.524 ms per env step for 1 / 2 / 4 / 8
-UPLOAD_CHUNKS = int(os.environ.get("PPO_AMD_UPLOAD_CHUNKS", "2"))
-# discrete policies: sample the actions inside the dense + heads launch of the rollout forward (one launch less per group
-# and env step; same bits)
-FUSE_ACT = int(os.environ.get("PPO_AMD_FUSE_ACT", "1"))
+UPLOAD_CHUNKS = 2
 
 
 def _p(t):
@@ -154,7 +146,6 @@ class Runner:
         # otherwise one draw from the run's host RNG (the reference's unseeded default gives a different stream per
         # run, rl/config.py:749); saved in checkpoints so that a resumed run continues the same streams
         self._device_seed = int(args.seed) if args.seed >= 0 else int(np.random.randint(1, 2**31 - 1))
-        self._graphs = {}
         self._step_events = []
         self._phase_stats = {}
         self.timers = {}
@@ -317,29 +308,7 @@ class Runner:
         hv = val.heads(val.encode(obs, train=False, tag=tag), tag) if self.dual else hp
         return hp, hv
 
-    def _rollout_graph(self, i, B, stream):
-        """Opt-in (PPO_AMD_ROLLOUT_GRAPH=1): hipGraph of one env group's policy forward (encoder + heads,
-        ~25 launches) from a fixed staging buffer to the fixed head-row buffer.  Weights are read in place, so
-        the graph stays valid across optimiser steps.  Returns None (eager path) when off or unavailable."""
-        key = (i, B)
-        if key not in self._graphs:
-            graph = None
-            if ROLLOUT_GRAPH:
-                try:
-                    stage = torch.zeros((B, *self.state_shape), dtype=self.all_obs.dtype, device=self.device)
-                    tag = f"i{i}"
-                    self._forward_heads(stage, tag)  # warm-up: scratch buffers, kernel attributes
-                    torch.cuda.synchronize()
-                    g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g, stream=stream):
-                        hp, hv = self._forward_heads(stage, tag)
-                    graph = (g, stage, hp, hv)
-                except Exception as e:  # capture not supported: keep the eager path
-                    self.log.warn(f"rollout hipGraph capture failed ({type(e).__name__}: {e}); running eagerly")
-            self._graphs[key] = graph
-        return self._graphs[key]
-
-    def _policy_step(self, t, lo=0, hi=None, tag="i", graph=None):
+    def _policy_step(self, t, lo=0, hi=None, tag="i"):
         """Forward + action sampling for envs [lo, hi) at env step t; writes those columns of row t of the
         rollout buffers.  The sampling counter is keyed by (rollout, t, env, action), so splitting the envs
         into groups does not change which action any env takes.  Dual architecture: the policy comes from
@@ -360,17 +329,14 @@ class Runner:
 
         values = None if self.dual else self.value.data_ptr() + first * self.value.stride(1) * 4
         discrete = self.action_dist == "discrete"
-        if graph is not None:
-            g, _stage, hp, hv = graph
-            g.replay()
-        else:
-            if discrete and FUSE_ACT:
-                # the sampling rides on the policy net's dense + heads launch when that forward replays its recorded
-                # launch list (models.DualHeadNet.encode); otherwise the tail comes back and is launched below
-                pol.act_tail = (nA, 1.0, seed & (2**64 - 1), counter, row(self.log_policy), row(self.actions),
-                                row(self.log_pac), row(self.raw_policy), values, self.VH)
-            hp, hv = self._forward_heads(self.all_obs[t, lo:hi], tag)
-        sampled = discrete and graph is None and FUSE_ACT and pol.act_tail is None
+        if discrete:
+            # the sampling rides on the policy net's dense + heads launch (one launch less per group and env step; same
+            # bits) when that forward replays its recorded launch list (models.DualHeadNet.encode); otherwise the tail
+            # comes back and is launched below
+            pol.act_tail = (nA, 1.0, seed & (2**64 - 1), counter, row(self.log_policy), row(self.actions),
+                            row(self.log_pac), row(self.raw_policy), values, self.VH)
+        hp, hv = self._forward_heads(self.all_obs[t, lo:hi], tag)
+        sampled = discrete and pol.act_tail is None
         pol.act_tail = None
 
         if sampled:
@@ -524,8 +490,7 @@ class Runner:
         for s_ in streams:
             if s_ is not main:
                 s_.wait_stream(main)
-        graphs = [self._rollout_graph(i, bounds[i + 1] - bounds[i], streams[i]) if P > 1 else None for i in range(P)]
-        for n in self._split_nets_active:  # (after the graph captures: a recorded graph keeps the one-workgroup launch)
+        for n in self._split_nets_active:
             n.allow_chain_split = True
         norm = self.model.obs_norm
 
@@ -544,22 +509,15 @@ class Runner:
             # runs 2 x 257 times per rollout and the host is on the critical path; the caller restores the stream)
             torch.cuda.set_stream(copy_stream)
             for leaf, lo, hi in (leaves[i] if only is None else [only]):
-                if graphs[i] is not None:  # the graph reads a fixed staging buffer; the rollout row is a D2D copy of it
-                    graphs[i][1][lo - bounds[i]:hi - bounds[i]].copy_(leaf.obs_t, non_blocking=True)
-                else:
-                    self.all_obs[t, lo:hi].copy_(leaf.obs_t, non_blocking=True)
+                self.all_obs[t, lo:hi].copy_(leaf.obs_t, non_blocking=True)
 
         def enqueue(i, t):
             # policy + sampling for group i at step t behind its upload (issued when its envs were stepped), actions D2H;
             # all async
             lo, hi = bounds[i], bounds[i + 1]
-            if graphs[i] is not None:
-                torch.cuda.set_stream(copy_stream)
-                copy_events[i].record()
-                self.all_obs[t, lo:hi].copy_(graphs[i][1], non_blocking=True)
             torch.cuda.set_stream(streams[i])
             streams[i].wait_event(copy_events[i])
-            self._policy_step(t, lo, hi, tag=tags[i], graph=graphs[i])
+            self._policy_step(t, lo, hi, tag=tags[i])
             if t < N:
                 host_rows[i].copy_(self.actions[t, lo:hi], non_blocking=True)
                 events[i].record()
@@ -569,7 +527,7 @@ class Runner:
             # each leaf's next observations going up as soon as they exist
             events[i].synchronize()
             for leaf, lo, hi in leaves[i]:
-                if norm is None and graphs[i] is None and UPLOAD_CHUNKS > 1 and hasattr(leaf, "step_upload"):
+                if norm is None and UPLOAD_CHUNKS > 1 and hasattr(leaf, "step_upload"):
                     # stepping and upload in one call: each quarter of the group goes up while the rest is stepped
                     torch.cuda.set_stream(copy_stream)
                     leaf.step_upload(act_np[lo:hi], rew_np[t, lo:hi], done_np[t, lo:hi], self.all_obs[t + 1, lo:hi],
@@ -644,7 +602,7 @@ class Runner:
         for s_ in streams:
             if s_ is not main:
                 main.wait_stream(s_)
-        main.wait_stream(copy_stream)  # the graph path's last all_obs rows are written by D2D copies queued there
+        main.wait_stream(copy_stream)  # as in the normalised path above: the next phase starts behind every upload
         self.time = self.all_time[N].copy()
         self.obs = parts[0].obs if P == 1 else np.concatenate([p.obs for p in parts])
 

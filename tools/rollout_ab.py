@@ -1,7 +1,7 @@
 """Interleaved A/B of rollout switches inside ONE process (run-to-run variation between processes on a GPU box is several
 per cent, more than most of these switches move): variants alternate rollout by rollout on the same Runner.
 Usage: [PPO_EXTRA_ARGS="--agents=1024 ..."] python tools/rollout_ab.py [n_steps] [rounds]
-variants: models.FUSE_BLOCK, models.CHAIN_SPLIT, rollout.FUSE_ACT; PPO_AB=conv1: the first layer's two kernels
+variants: models.FUSE_BLOCK, models.CHAIN_SPLIT; PPO_AB=chunks: rollout.UPLOAD_CHUNKS; PPO_AB=conv1: the first layer's two kernels
 (ppo_conv1_pool_form: LDS form / pooled out of the accumulators), everything else on"""
 import os
 import sys
@@ -28,27 +28,22 @@ model = models.TVFModel("impala", input_dims=shape, actions=nA, device="cuda", a
 r = rollout.Runner(model, logger.Logger(quiet=True))
 r.vec_env = envs.create_envs_classic()
 r.reset()
-variants = {"base": (0, 0, 0), "block": (1, 0, 0), "block+act": (1, 0, 1), "block+split": (1, 1, 0), "block+split+act": (1, 1, 1)}
+variants = {"base": (0, 0), "block": (1, 0), "block+split": (1, 1)}
 if os.environ.get("PPO_AB") == "chunks":  # pieces a group's observations go up in (all kernel switches on)
-    variants = {f"upload chunks {c}": (1, 1, 1, c) for c in (1, 2, 4, 8)}
-if os.environ.get("PPO_AB") == "graph":  # hipGraph of a group's forward (fixed staging buffer, separate sampling launch)
-    variants = {"eager": (1, 1, 1, 2, 0), "graph": (1, 1, 1, 2, 1)}
+    variants = {f"upload chunks {c}": (1, 1, c) for c in (1, 2, 4, 8)}
 conv1_form = None
 if os.environ.get("PPO_AB") == "conv1":
     from ppo_amd import _lib
     conv1_form = {"first layer: LDS form": 1, "first layer: from the accumulators": 0}
-    variants = {k: (1, 1, 1) for k in conv1_form}
+    variants = {k: (1, 1) for k in conv1_form}
 times = {k: [] for k in variants}
 for rnd in range(rounds + 1):
-    for name, (blk, split, act, *rest) in variants.items():
-        models.FUSE_BLOCK, models.CHAIN_SPLIT, rollout.FUSE_ACT = blk, split, act
+    for name, (blk, split, *rest) in variants.items():
+        models.FUSE_BLOCK, models.CHAIN_SPLIT = blk, split
         if conv1_form:
             _lib.load().ppo_conv1_pool_form(conv1_form[name])
         if rest:
             rollout.UPLOAD_CHUNKS = rest[0]
-        if len(rest) > 1:
-            rollout.ROLLOUT_GRAPH = rest[1]
-            r._graphs.clear()
         model.policy_net._plans.clear()
         r.generate_rollout()  # records the launch lists of this variant
         torch.cuda.synchronize()
