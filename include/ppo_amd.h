@@ -562,6 +562,7 @@ int ppo_impala_stack_tail_backward_f32(const float *g, const float *const *packe
  * block0.conv0, firstconv); masks: HOST array of 4 forward maps (a1, q0, a0, p).  Writes da1, g1, da0, g0 (as
  * ppo_impala_stack_tail_backward_f32), dc = ppo_maxpool3x3s2_backward_f32(g0, argmax) [n,C,h,w] and
  * g_prev = ppo_conv3x3_backward_data_packed_f32(dc, firstconv) [n,C,h,w], all bit-identical to those launches.
+ * argmax must be 4-byte aligned (PPO_E_ALIGN): the kernel fetches an image's bytes as words.
  */
 int ppo_impala_stack_full_supported(int channels, int h, int w);
 /* Chained form: the PREVIOUS stack's two residual blocks (on `in` = its pooled map [n,C,h,w]; pre_* as the tail
@@ -585,6 +586,18 @@ int ppo_impala_stack_chain_split_forward_f32(const float *in, const float *const
 int ppo_impala_stack_full_backward_f32(const float *g, const float *const *packed_weights_t, const float *const *masks,
                                        const uint8_t *argmax, float *da1, float *g1, float *da0, float *g0, float *dc,
                                        float *g_prev, int n_images, int channels, int h, int w, void *stream);
+/* Chained backward-data: ppo_impala_stack_full_backward_f32 of this stack, then - on g_prev, still resident - the
+ * PREVIOUS stack's two blocks as ppo_impala_stack_tail_backward_f32 at h x w (post_packed_weights_t / post_masks: HOST
+ * arrays of 4, in that entry point's order; post_da1, post_g1, post_da0, post_g0 [n,C,h,w]), one launch.  All ten maps
+ * are written and required, each bit-identical to the launches this replaces (tail at HO x WO, max-pool backward,
+ * transposed first convolution, tail at h x w).  PPO_E_INVALID on a null pointer or a geometry without a kernel
+ * (ppo_impala_stack_full_supported), PPO_E_ALIGN when a packed weight is not 16-byte aligned or argmax not 4-byte
+ * aligned; n_images = 0 is a no-op. */
+int ppo_impala_stack_chain_backward_f32(const float *g, const float *const *packed_weights_t, const float *const *masks,
+                                        const uint8_t *argmax, float *da1, float *g1, float *da0, float *g0, float *dc,
+                                        float *g_prev, const float *const *post_packed_weights_t,
+                                        const float *const *post_masks, float *post_da1, float *post_g1, float *post_da0,
+                                        float *post_g0, int n_images, int channels, int h, int w, void *stream);
 int ppo_impala_stack_full_forward_f32(const float *in, const float *const *packed_weights, const float *const *biases,
                                       float *pooled, uint8_t *argmax, float *a0, float *q0, float *a1, float *q1,
                                       int n_images, int channels, int h, int w, void *stream);

@@ -592,8 +592,14 @@ __device__ __forceinline__ void resident_conv(float *smem, int src_off, int dst_
     for (int n = 0; n < NT; ++n)
 #pragma unroll
         for (int r = 0; r < 4; ++r) bias_r[n][r] = (GATED || !bias) ? 0.f : bias[(n0 + n) * 16 + g * 4 + r];
+    // The gate of a layer with many pixel tiles per lane is requested half-way through the K loop, into registers the
+    // first half's A operand has left: requested up front (as the small maps still do) it is MT * NT * 4 registers
+    // held across the whole loop, which the 21x21 layers of the chained backward do not have.
+    constexpr int SB = (MT * NT >= 4) ? 2 : 4;
+    constexpr int NB = (KS + SB - 1) / SB;
+    constexpr int GATE_AT = (GATED && MT * NT * 4 > 16) ? NB / 2 : -1;
     float gate[GATED ? MT : 1][NT][4];
-    if constexpr (GATED) {
+    auto load_gate = [&]() {
         const __amdgpu_buffer_rsrc_t mask_b = buffer_of(mask);  // range-checked reads (common.h)
 #pragma unroll
         for (int m = 0; m < MT; ++m)
@@ -603,7 +609,8 @@ __device__ __forceinline__ void resident_conv(float *smem, int src_off, int dst_
                 for (int r = 0; r < 4; ++r)
                     gate[m][n][r] = buffer_f32(mask_b, lm.pix[m] < H * W ? (((n0 + n) * 16 + g * 4 + r) * (H * W) + lm.pix[m]) * 4
                                                                          : kOutside);  // unused beyond the map
-    }
+    };
+    if constexpr (GATED && GATE_AT < 0) load_gate();
 
     __syncthreads();  // the source map is complete
     int base[MT];
@@ -615,8 +622,6 @@ __device__ __forceinline__ void resident_conv(float *smem, int src_off, int dst_
 #pragma unroll
         for (int m = 0; m < MT; ++m) acc[n][m] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    constexpr int SB = (MT * NT >= 4) ? 2 : 4;
-    constexpr int NB = (KS + SB - 1) / SB;
     float raw[2][SB][MT];
     auto load_block = [&](int j, float (&r)[SB][MT]) {
 #pragma unroll
@@ -654,6 +659,7 @@ __device__ __forceinline__ void resident_conv(float *smem, int src_off, int dst_
         }
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (j + 1 < NB) load_block(j + 1, raw[(j + 1) & 1]);
+        if constexpr (j == GATE_AT) load_gate();
 #pragma unroll
         for (int u = 0; u < SB; ++u) {
             const int s = j * SB + u;
@@ -780,6 +786,13 @@ __global__ __launch_bounds__(NW * NSPLIT * 64) void stack_full_kernel(StackFullA
 //   da1, g1, da0, g0 as ppo_impala_stack_tail_backward_f32;  dc = maxpool_bwd(g0, argmax)  (summation order of
 //   maxpool_bwd_kernel: windows (oy0, k), (oy0, k + 1), (oy0 + 1, k), (oy0 + 1, k + 1));  g_prev = conv_first^T(dc).
 // All of them go to HBM as well: the weight-gradient kernels read them.
+//
+// Chained form (`has_post`, the mirror of stack_full_kernel's `has_pre`): g_prev is the gradient of the PREVIOUS stack's
+// output and lies resident in map A, so that stack's gated transposed block chain runs on it right there (A <-> B
+// ping-pong as stack_tail_kernel<.., BACKWARD>, its da1, g1, da0, g0 written to HBM): the 21x21 gradient map is not read
+// back and three kernel boundaries of a strictly dependent chain go.  Map A is then a convolution SOURCE, so its halo rows
+// and guards - leftovers of the small maps X and Y - are cleared once the pool gather has read X; B's stay zero from the
+// kernel's start (only interiors are ever written).
 struct StackFullBwdArgs {
     const float *g;         // [n, C, HO, WO] d loss / d (stack output)
     const float *w[5];      // backward-data packed weights: block1.conv1, block1.conv0, block0.conv1, block0.conv0, firstconv
@@ -788,6 +801,11 @@ struct StackFullBwdArgs {
     float *save[4];         // da1, g1, da0, g0
     float *dc;              // [n, C, HI, WI]
     float *g_prev;          // [n, C, HI, WI]
+    const float *post_w[4];     // chained form: the previous stack's backward-data packed weights (block1.conv1,
+                                // block1.conv0, block0.conv1, block0.conv0) ...
+    const float *post_mask[4];  // ... its a1, q0, a0, p ([n, C, HI, WI]) ...
+    float *post_save[4];        // ... and its da1, g1, da0, g0 ([n, C, HI, WI], all required)
+    int has_post;
     int n_images;
 };
 
@@ -797,6 +815,7 @@ __global__ __launch_bounds__(NW * NSPLIT * 64) void stack_full_bwd_kernel(StackF
     using SI = StackCfg<C, HI, WI, MTI, NW, NSPLIT>;
     using SO = StackCfg<C, HO, WO, MTO, NW, NSPLIT>;
     static_assert(2 * SO::LDS_MAP <= SI::LDS_MAP, "the small maps live inside the first big map's LDS");
+    static_assert(C * HO * WO <= SO::LDS_MAP * 4, "the argmax bytes of an image fit the second small map");
     constexpr int NT = SI::NTL, WAVES = SI::WAVES, THREADS = WAVES * 64;
     constexpr int A_OFF = 0, B_OFF = SI::LDS_MAP, X_OFF = 0, Y_OFF = SO::LDS_MAP;
     extern __shared__ __align__(16) float smem[];
@@ -816,6 +835,16 @@ __global__ __launch_bounds__(NW * NSPLIT * 64) void stack_full_bwd_kernel(StackF
         __syncthreads();
         stage_band_chunk_dma<C, HO, WO, SO::ROWS, SO::PLANE, SO::G, WAVES>(a.g, img, 0, smem + X_OFF, tid);
         const size_t small_img = (size_t)img * C * HO * WO, big_img = (size_t)img * C * HI * WI;
+        // this image's argmax bytes are requested now and parked in Y when the blocks are through with it: the gather
+        // below reads each of them four times, and from HBM every round of it waited out a memory latency
+        constexpr int AM_WORDS = C * HO * WO / 4, AM_PER = (AM_WORDS + THREADS - 1) / THREADS;
+        static_assert(C * HO * WO % 4 == 0, "an image's argmax bytes are whole words (the entry points check the base)");
+        uint32_t am_r[AM_PER];
+#pragma unroll
+        for (int k = 0; k < AM_PER; ++k) {
+            const int i = tid + k * THREADS;
+            am_r[k] = reinterpret_cast<const uint32_t *>(a.argmax + small_img)[i < AM_WORDS ? i : 0];
+        }
 #pragma unroll 1
         for (int layer = 0; layer < 4; ++layer) {
             const int odd = layer & 1;
@@ -823,10 +852,16 @@ __global__ __launch_bounds__(NW * NSPLIT * 64) void stack_full_bwd_kernel(StackF
                                                                    a.w[layer], nullptr, a.save[layer] + small_img, lmo, n0,
                                                                    lane, a.mask[layer] + small_img);
         }
-        __syncthreads();  // g0 is complete in X
-        // ---- max-pool backward: gather per pre-pool pixel, X (g0) + argmax -> B (dc) and HBM
+        __syncthreads();  // g0 is complete in X and nobody reads Y (da0) any more
+        const uint8_t *am = reinterpret_cast<const uint8_t *>(smem + Y_OFF);
+#pragma unroll
+        for (int k = 0; k < AM_PER; ++k) {
+            const int i = tid + k * THREADS;
+            if (i < AM_WORDS) reinterpret_cast<uint32_t *>(smem + Y_OFF)[i] = am_r[k];
+        }
+        __syncthreads();
+        // ---- max-pool backward: gather per pre-pool pixel, X (g0) + argmax (Y) -> B (dc) and HBM
         {
-            const uint8_t *am = a.argmax + small_img;
             for (int e = tid; e < C * HI * WI; e += THREADS) {
                 const int co = e / (HI * WI), r = e % (HI * WI);
                 const int iy = r / WI, ix = r % WI;
@@ -853,9 +888,24 @@ __global__ __launch_bounds__(NW * NSPLIT * 64) void stack_full_bwd_kernel(StackF
                 a.dc[big_img + e] = sum;
             }
         }
-        // ---- first convolution, transposed: B (dc) -> A (overwrites the small maps; its barrier publishes B)
+        if (a.has_post) {
+            __syncthreads();  // the gather has read X for the last time
+            zero_lds<SI::LDS_MAP, THREADS>(smem + A_OFF, tid);  // A becomes a source below: its halo rows and guards
+        }
+        // ---- first convolution, transposed: B (dc) -> A (overwrites the small maps; its barrier publishes B and A's zeros)
         resident_conv<C, HI, WI, MTI, SI::NT, NT, false, false>(smem, B_OFF, A_OFF, false, a.w[4], nullptr,
                                                                 a.g_prev + big_img, lmi, n0, lane);
+        if (a.has_post) {
+            // ---- the previous stack's gated transposed blocks on g_prev: A -> B, B -> A (+= A), twice; g0 ends in A.
+            // Every layer overwrites the whole interior of its destination and nothing else (B: dc, then da1, da0).
+#pragma unroll 1
+            for (int layer = 0; layer < 4; ++layer) {
+                const int odd = layer & 1;
+                resident_conv<C, HI, WI, MTI, SI::NT, NT, false, true>(smem, odd ? B_OFF : A_OFF, odd ? A_OFF : B_OFF, odd != 0,
+                                                                       a.post_w[layer], nullptr, a.post_save[layer] + big_img,
+                                                                       lmi, n0, lane, a.post_mask[layer] + big_img);
+            }
+        }
     }
 }
 
@@ -1273,6 +1323,7 @@ extern "C" int ppo_impala_stack_full_backward_f32(const float *g, const float *c
     if (n_images == 0) return PPO_OK;
     if (!g || !packed_weights_t || !masks || !argmax || !da1 || !g1 || !da0 || !g0 || !dc || !g_prev)
         return fail(PPO_E_INVALID, "ppo_impala_stack_full_backward_f32: null pointer");
+    if (!aligned(argmax, 4)) return fail(PPO_E_ALIGN, "ppo_impala_stack_full_backward_f32: argmax must be 4-byte aligned");
     StackFullBwdArgs args;
     args.g = g;
     for (int l = 0; l < 5; ++l) {
@@ -1290,12 +1341,66 @@ extern "C" int ppo_impala_stack_full_backward_f32(const float *g, const float *c
     args.save[3] = g0;
     args.dc = dc;
     args.g_prev = g_prev;
+    for (int l = 0; l < 4; ++l) {
+        args.post_w[l] = nullptr;
+        args.post_mask[l] = nullptr;
+        args.post_save[l] = nullptr;
+    }
+    args.has_post = 0;
     args.n_images = n_images;
     if (channels == 32 && h == 21 && w == 21)
         return launch_stack_full_bwd<32, 21, 21, 7, 11, 11, 2, 4, 2>(args, as_stream(stream));
     if (channels == 32 && h == 16 && w == 16)
         return launch_stack_full_bwd<32, 16, 16, 4, 8, 8, 1, 4, 2>(args, as_stream(stream));
     return fail(PPO_E_INVALID, "ppo_impala_stack_full_backward_f32: no kernel for %d channels at %dx%d", channels, h, w);
+}
+
+extern "C" int ppo_impala_stack_chain_backward_f32(const float *g, const float *const *packed_weights_t,
+                                                   const float *const *masks, const uint8_t *argmax, float *da1, float *g1,
+                                                   float *da0, float *g0, float *dc, float *g_prev,
+                                                   const float *const *post_packed_weights_t, const float *const *post_masks,
+                                                   float *post_da1, float *post_g1, float *post_da0, float *post_g0,
+                                                   int n_images, int channels, int h, int w, void *stream)
+{
+    using namespace ppo;
+    if (n_images < 0) return fail(PPO_E_INVALID, "ppo_impala_stack_chain_backward_f32: negative batch");
+    if (n_images == 0) return PPO_OK;
+    if (!g || !packed_weights_t || !masks || !argmax || !da1 || !g1 || !da0 || !g0 || !dc || !g_prev || !post_packed_weights_t
+        || !post_masks || !post_da1 || !post_g1 || !post_da0 || !post_g0)
+        return fail(PPO_E_INVALID, "ppo_impala_stack_chain_backward_f32: null pointer");
+    if (!aligned(argmax, 4)) return fail(PPO_E_ALIGN, "ppo_impala_stack_chain_backward_f32: argmax must be 4-byte aligned");
+    StackFullBwdArgs args;
+    args.g = g;
+    for (int l = 0; l < 5; ++l) {
+        if (!packed_weights_t[l] || (l < 4 && (!masks[l] || !post_packed_weights_t[l] || !post_masks[l])))
+            return fail(PPO_E_INVALID, "ppo_impala_stack_chain_backward_f32: null weights / mask of layer %d", l);
+        if (!aligned(packed_weights_t[l], 16) || (l < 4 && !aligned(post_packed_weights_t[l], 16)))
+            return fail(PPO_E_ALIGN, "ppo_impala_stack_chain_backward_f32: packed weights must be 16-byte aligned");
+        args.w[l] = packed_weights_t[l];
+        if (l < 4) {
+            args.mask[l] = masks[l];
+            args.post_w[l] = post_packed_weights_t[l];
+            args.post_mask[l] = post_masks[l];
+        }
+    }
+    args.argmax = argmax;
+    args.save[0] = da1;
+    args.save[1] = g1;
+    args.save[2] = da0;
+    args.save[3] = g0;
+    args.dc = dc;
+    args.g_prev = g_prev;
+    args.post_save[0] = post_da1;
+    args.post_save[1] = post_g1;
+    args.post_save[2] = post_da0;
+    args.post_save[3] = post_g0;
+    args.has_post = 1;
+    args.n_images = n_images;
+    if (channels == 32 && h == 21 && w == 21)
+        return launch_stack_full_bwd<32, 21, 21, 7, 11, 11, 2, 4, 2>(args, as_stream(stream));
+    if (channels == 32 && h == 16 && w == 16)
+        return launch_stack_full_bwd<32, 16, 16, 4, 8, 8, 1, 4, 2>(args, as_stream(stream));
+    return fail(PPO_E_INVALID, "ppo_impala_stack_chain_backward_f32: no kernel for %d channels at %dx%d", channels, h, w);
 }
 
 extern "C" size_t ppo_impala_stack_chain_split_workspace_bytes(int n_images, int channels, int h, int w)

@@ -75,13 +75,19 @@ FUSE_STACK_CHAIN = int(os.environ.get("PPO_AMD_FUSE_STACK_CHAIN", "1"))
 CHAIN_SPLIT = int(os.environ.get("PPO_AMD_CHAIN_SPLIT", "1"))
 CHAIN_SPLIT_MAX_BATCH = 128
 # ... and its backward-data pass (blocks + max-pool backward + transposed first convolution) likewise.  Off by default:
-# bit-identical, but 1.445 ms per 256-sample step against 1.395 without it (measured while the weight-gradient kernels
-# still ran on a second stream: it holds a whole CU's LDS, so they got nothing to overlap with for its duration, and it
-# releases the five gradients they wait for only at its end).
+# bit-identical, and on its own it has not been measured faster than the launches it replaces (see
+# profiles/chain_backward.md for the single-stream figures); the chained form below is what runs at training batches.
 FUSE_STACK_FULL_BWD = int(os.environ.get("PPO_AMD_FUSE_STACK_FULL_BWD", "0"))
 # ... and the same for their backward-data chain, as a bit mask over the stacks (per 256-sample step, same box:
 # 1.476 ms with mask 0, 1.450 with 4 (11x11), 1.404 with 2 (21x21), 1.408 with 6).
 FUSE_STACK_TAIL_BWD = int(os.environ.get("PPO_AMD_FUSE_STACK_TAIL_BWD", "7"))
+# The backward-data pass of the last stack AND of the previous stack's blocks as one launch
+# (ppo_impala_stack_chain_backward_f32, the mirror of the chained forward: the gradient of the previous stack's output
+# stays in LDS) instead of four: tail at 11x11, max-pool backward, transposed first convolution, tail at 21x21.  Same
+# bits.  One workgroup per image, so small batches idle the chip and keep the four launches: the chained launch runs
+# from FUSE_CHAIN_BWD_MIN_BATCH images up (interleaved A/B, profiles/chain_backward.md: 1.0841 -> 1.0676 ms per
+# minibatch of 256, a tie at 128, 11 us slower at 64).
+FUSE_CHAIN_BWD_MIN_BATCH = 192
 # The 16-channel stack's blocks (42x42 / 32x32: the map fills most of a CU's LDS) as the in-place, row-shifted form of the
 # same kernel family (csrc/stack_fused.hip stack_shift_kernel) instead of four convolution launches.  One 16-wave workgroup per
 # image and per CU, two wave groups half a band apart (one in its K loop while the other runs its epilogue): measured at
@@ -1350,8 +1356,36 @@ class DualHeadNet:
                          ctypes.addressof(n_slabs))
             slab_launch(args_, n_slabs, [(wname, ws) for (_x, _dy, wname), ws in zip(problems, wss)], c, c)
 
+        chained = None  # (si, g0): stack si's blocks went through the chained launch of stack si + 1
         for si in reversed(range(len(sp.stacks))):
             cin, cout, hh, ww, ho, wo = sp.stacks[si]
+            chain_w = self._stack_chain_bwd_ptrs(si, B) if chained is None else None
+            if chain_w is not None:
+                # this stack's backward-data pass and the previous stack's blocks in one launch; the weight-gradient
+                # launches are those of the separate launches, reading the same buffers
+                pi = si - 1
+                names = ("_1_da", "_1_in", "_0_da", "_0_in")
+                da1, g1, da0, g0 = (self._buf(f"g{si}{nm}", (B, cout, ho, wo)) for nm in names)
+                pda1, pg1, pda0, pg0 = (self._buf(f"g{pi}{nm}", (B, cin, hh, ww)) for nm in names)
+                dc = self._buf(f"g{si}_dc", (B, cout, hh, ww))
+                g_prev = self._buf(f"g{pi}_top", (B, cin, hh, ww))
+                p_in, a0, q0, a1 = acts[f"q{si}_0_in"], acts[f"a{si}_0"], acts[f"q{si}_1_in"], acts[f"a{si}_1"]
+                masks = (ctypes.c_void_p * 4)(a1.data_ptr(), q0.data_ptr(), a0.data_ptr(), p_in.data_ptr())
+                pmasks = (ctypes.c_void_p * 4)(*[acts[k].data_ptr() for k in
+                                                 (f"a{pi}_1", f"q{pi}_1_in", f"a{pi}_0", f"q{pi}_0_in")])
+                self._call("ppo_impala_stack_chain_backward_f32", _p(g), chain_w[0], masks, _p(acts[f"idx{si}"]), _p(da1),
+                           _p(g1), _p(da0), _p(g0), _p(dc), _p(g_prev), chain_w[1], pmasks, _p(pda1), _p(pg1), _p(pda0),
+                           _p(pg0), B, cout, hh, ww)
+                b0, b1 = f"encoder.stacks.{si}.blocks.0", f"encoder.stacks.{si}.blocks.1"
+                wgrad_blocks([(a1, g, b1 + ".conv1"), (q0, da1, b1 + ".conv0"), (a0, g1, b0 + ".conv1"),
+                              (p_in, da0, b0 + ".conv0")], B, cout, ho, wo)
+                if WGRAD_RIDE and WGRAD_BATCH_LAUNCH:
+                    carry.append((acts[f"in{si}"], dc, f"encoder.stacks.{si}.firstconv", B, cin, hh, ww))
+                else:
+                    wgrad(acts[f"in{si}"], IN_NONE, dc, f"encoder.stacks.{si}.firstconv", B, cin, cout, hh, ww)
+                g = g_prev
+                chained = (pi, pg0)
+                continue
             # blocks + max-pool backward + transposed first convolution of the stack in one launch, ...
             full_w = self._stack_full_bwd_ptrs(si, cin, cout, hh, ww) if si > 0 else None
             # ... or the four backward-data convolutions of the stack's blocks in one launch (csrc/stack_fused.hip), ...
@@ -1359,7 +1393,16 @@ class DualHeadNet:
             # ... which in split mode is the gated transposed chain of this stack's blocks as the split-bf16 launch
             split = full_w is None and self.split_bf16 and (si, 1) in self._pk16
             fused = full_w is not None or tail_w is not None or split
-            if fused:
+            if chained is not None and chained[0] == si:
+                # the chained launch above ran this stack's blocks: their weight gradients, then the pool and first conv
+                fused, full_w = True, None
+                b0, b1 = f"encoder.stacks.{si}.blocks.0", f"encoder.stacks.{si}.blocks.1"
+                p_in, a0, q0, a1 = acts[f"q{si}_0_in"], acts[f"a{si}_0"], acts[f"q{si}_1_in"], acts[f"a{si}_1"]
+                wgrad_blocks([(a1, g, b1 + ".conv1"), (q0, self._buf(f"g{si}_1_da", (B, cout, ho, wo)), b1 + ".conv0"),
+                              (a0, self._buf(f"g{si}_1_in", (B, cout, ho, wo)), b0 + ".conv1"),
+                              (p_in, self._buf(f"g{si}_0_da", (B, cout, ho, wo)), b0 + ".conv0")], B, cout, ho, wo)
+                g = chained[1]
+            elif fused:
                 b0, b1 = f"encoder.stacks.{si}.blocks.0", f"encoder.stacks.{si}.blocks.1"
                 p_in, a0, q0, a1 = acts[f"q{si}_0_in"], acts[f"a{si}_0"], acts[f"q{si}_1_in"], acts[f"a{si}_1"]
                 da1, g1, da0, g0 = (self._buf(nm, (B, cout, ho, wo)) for nm in
@@ -1452,6 +1495,30 @@ class DualHeadNet:
                 return None
             cached = (ctypes.c_void_p * 5)(*[pk.data_ptr() for pk in pks])
             self._tail_ptrs[("full_bwd", si)] = cached
+        return cached
+
+    def _stack_chain_bwd_ptrs(self, si, batch):
+        """(the five backward-data packed weights of stack si, the four of stack si - 1's blocks) as host arrays in
+        processing order, or None when ppo_impala_stack_chain_backward_f32 does not apply: exact float32 only, two blocks
+        per stack, both stacks of one channel count at a geometry the whole-stack kernels have, and a batch that fills
+        the chip (one workgroup per image)."""
+        if si < 1 or self.split_bf16 or batch < FUSE_CHAIN_BWD_MIN_BATCH or self.spec.n_block != 2 \
+                or not (FUSE_STACK_TAIL and FUSE_STACK_TAIL_BWD >> si & 1 and FUSE_STACK_TAIL_BWD >> (si - 1) & 1):
+            return None
+        cin, cout, h, w, _ho, _wo = self.spec.stacks[si]
+        if cin != cout or self.spec.stacks[si - 1][1] != cin or tuple(self.spec.stacks[si - 1][4:6]) != (h, w) \
+                or not self.lib.ppo_impala_stack_full_supported(cout, h, w):
+            return None
+        cached = self._tail_ptrs.get(("chain_bwd", si))
+        if cached is None:
+            names = [f"encoder.stacks.{s_}.blocks.{bi}.conv{ci}" for s_ in (si, si - 1) for bi in (1, 0) for ci in (1, 0)]
+            names.insert(4, f"encoder.stacks.{si}.firstconv")
+            pks = [self._pk.get((n, 1)) for n in names]
+            if any(pk is None for pk in pks):
+                return None
+            cached = ((ctypes.c_void_p * 5)(*[pk.data_ptr() for pk in pks[:5]]),
+                      (ctypes.c_void_p * 4)(*[pk.data_ptr() for pk in pks[5:]]))
+            self._tail_ptrs[("chain_bwd", si)] = cached
         return cached
 
     def _stack_tail_bwd_ptrs(self, si, cout, ho, wo):
