@@ -293,6 +293,25 @@ int ppo_conv2d_strided_backward_weight_f32(const void *in, int in_mode, const fl
                                            int w, int cout, int kh, int kw, int stride, void *stream);
 
 /*
+ * The three launches above with F.leaky_relu(., negative_slope) behind the convolution instead of F.relu: the layers of
+ * the reference's RNDTarget / RNDPredictor (rl/models.py:228-230, 250-252, 270-272, 291-293; slope 0.2 there).
+ * Forward stores v > 0 ? v : negative_slope * v.  The backward forms scale dy by (gate > 0 ? 1 : negative_slope),
+ * torch's leaky_relu backward (the slope branch at 0); gate is the forward's stored activation, which has the sign of
+ * the pre-activation because 0 < negative_slope <= 1 (anything else: PPO_E_INVALID); gate nullable: g = dy.
+ * Same kernel, same summation order, same workspace as the ReLU forms.
+ */
+int ppo_conv2d_strided_forward_leaky_f32(const void *in, int in_mode, const float *weight, const float *bias, float *out,
+                                         float negative_slope, int n, int cin, int h, int w, int cout, int kh, int kw,
+                                         int stride, void *stream);
+int ppo_conv2d_strided_backward_data_leaky_f32(const float *dy, const float *gate, const float *weight, float *dx,
+                                               float negative_slope, int n, int cin, int h, int w, int cout, int kh, int kw,
+                                               int stride, void *stream);
+int ppo_conv2d_strided_backward_weight_leaky_f32(const void *in, int in_mode, const float *dy, const float *gate,
+                                                 float *dweight, float *dbias, void *workspace, size_t workspace_bytes,
+                                                 float negative_slope, int n, int cin, int h, int w, int cout, int kh, int kw,
+                                                 int stride, void *stream);
+
+/*
  * C[m,n] = epi( sum_k fa(A[m,k]) * fb(B[k,n]) + bias[n] ),  f32 MFMA.
  * A element (m,k) at A[m*a_sm + k*a_sk]; B element (k,n) at B[k*b_sk + n*b_sn]; C row-major with ldc.
  * relu_a / relu_b: apply max(.,0) to that operand on load.  bias [N], mask [M,ldc] nullable;
@@ -493,6 +512,15 @@ int ppo_normalize_f32(const float *x, int64_t n, const double *moments, float ep
 /* dst[i] += src[i], i < n: gradient accumulation over the micro-batches of a minibatch (Runner.train_batch,
  * rl/rollout.py:2331-2374, where autograd accumulates into .grad across `loss_scale = 1 / micro_batches` passes). */
 int ppo_accumulate_f32(float *dst, const float *src, int64_t n, void *stream);
+/* out[i] = (float)((double)clamp(x[i], -clip, clip) / scale_div - mean), mean = moments[0] / moments[2] of a
+ * ppo_moments_f64 result (nullable: 0); clip <= 0: no clamp.  The normalisation of a rollout's intrinsic rewards
+ * (rl/rollout.py:929 clip to +-5, :1165 division by the float64 intrinsic_reward_norm_scale - a float64 division under
+ * NumPy >= 2 - and :1168 `--ir_center`).  out may be x. */
+int ppo_scale_shift_clip_f32(const float *x, int64_t n, float clip, double scale_div, const double *moments, float *out,
+                             void *stream);
+/* dst[i] += alpha * src[i], product and sum rounded separately as NumPy does: advantage += ir_scale * int_advantage
+ * (rl/rollout.py:1227-1228). */
+int ppo_axpy_f32(float *dst, const float *src, float alpha, int64_t n, void *stream);
 /* w[i] *= mask[i], mask in {0, 1}: DualHeadNet.mask_feature_weights (rl/models.py:425-427), the static feature mask of
  * the TVF head (--tvf_feature_sparsity / --tvf_feature_window, rl/models.py:386-421) re-applied after every optimiser
  * step (the reference re-applies it before every forward that evaluates the head, rl/models.py:494-497: same weights
@@ -621,6 +649,31 @@ int ppo_obs_rms_update_f64(const double *moments, double batch_count, double cou
                            float *mu, float *std, int F, void *stream);
 int ppo_obs_normalize_f32(const void *x, int is_u8, const float *mu, const float *std, float eps, float *out, int B,
                           int F, void *stream);
+/* One channel of the same transform, optionally through a row index: x [rows, C, H, W], mu / std [C, H, W],
+ * out[b, 0, :, :] = clamp((f(x[row(b), channel]) - mu[channel]) / (std[channel] + eps), -5, 5), row(b) = index ? index[b] : b
+ * (the caller validates indices), out contiguous [B, 1, H, W].  Bit-identical to ppo_obs_normalize_f32 restricted to
+ * that channel.  The input of the RND networks: prep_for_model, perform_normalization and `x[:, -1:]`
+ * (rl/models.py:719-723) and the minibatch gather (rl/rollout.py:2349-2372) in one launch. */
+int ppo_obs_normalize_channel_f32(const void *x, int is_u8, const int32_t *index, const float *mu, const float *std, float eps,
+                                  float *out, int B, int C, int H, int W, int channel, void *stream);
+
+/* ------------------------------------------------------------------------
+ * Random Network Distillation (csrc/rnd.hip): pred / target [B, F] are the outputs of RNDPredictor / RNDTarget.
+ *   err[b * err_stride] = mean_j (target[b,j] - pred[b,j])^2   (rl/models.py:736; err nullable; the stride lets a rollout
+ *                         write a group's columns of row t of its [N, A] intrinsic-reward buffer directly)
+ *   dpred[b,j]          = grad_scale * 2 (pred[b,j] - target[b,j]) / F   (nullable) - the gradient of
+ *                         grad_scale * sum_b err[b]; the caller passes loss_scale / B (rl/rollout.py:1804-1822)
+ *   stats (nullable, device float[PPO_RND_STATS], zeroed by the caller): a second, single-workgroup launch adds
+ *                         [0] sum_b err[b], [1] mean(target), [2] mean_j var_b(target[:,j]) (unbiased), [4] 1 and keeps
+ *                         [3] = max(., max |target|): the sums behind the reference's per-call rnd_features_mean / _var /
+ *                         _max (rl/models.py:732-734) without a host read.
+ *                         B = 1 puts NaN into [2], as torch.var of one row does, and the row keeps it: a caller that
+ *                         accumulates over minibatches passes B >= 2 (Runner.train_rnd refuses a minibatch of one).
+ * Fixed summation order, no atomics: every launch gives the same bits.
+ * ---------------------------------------------------------------------- */
+#define PPO_RND_STATS 5
+int ppo_rnd_error_f32(const float *pred, const float *target, int B, int F, float *err, int64_t err_stride, float *dpred,
+                      float grad_scale, float *stats, void *stream);
 
 /* ------------------------------------------------------------------------
  * Synthetic vectorised environment (HOST pointers; runs on host threads).

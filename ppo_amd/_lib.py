@@ -18,6 +18,7 @@ LIB_PATH = os.environ.get("PPO_AMD_LIB") or os.path.join(HERE, "lib", "libppo_am
 PPO_TERM_NONE, PPO_TERM_U8, PPO_TERM_F32 = 0, 1, 2
 PPO_SCAN_AUTO, PPO_SCAN_COLUMNS, PPO_SCAN_TILES = 0, 1, 2
 PPO_IN_NONE, PPO_IN_RELU, PPO_IN_U8 = 0, 1, 2
+PPO_RND_STATS = 5
 
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
@@ -136,6 +137,14 @@ SIGNATURES = {
     "ppo_conv2d_strided_backward_data_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "ppo_conv2d_strided_wgrad_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i, _i, _i]),
     "ppo_conv2d_strided_backward_weight_f32": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "ppo_conv2d_strided_forward_leaky_f32": (_i, [_vp, _i, _vp, _vp, _vp, _f, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "ppo_conv2d_strided_backward_data_leaky_f32": (_i, [_vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "ppo_conv2d_strided_backward_weight_leaky_f32": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _sz, _f, _i, _i, _i, _i, _i, _i, _i,
+                                                          _i, _vp]),
+    "ppo_obs_normalize_channel_f32": (_i, [_vp, _i, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _i, _i, _vp]),
+    "ppo_rnd_error_f32": (_i, [_vp, _vp, _i, _i, _vp, _i64, _vp, _f, _vp, _vp]),
+    "ppo_scale_shift_clip_f32": (_i, [_vp, _i64, _f, _d, _vp, _vp, _vp]),
+    "ppo_axpy_f32": (_i, [_vp, _vp, _f, _i64, _vp]),
     "ppo_adam_step_scatter_f32": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _d, _d, _d, _d, _f, _f, _vp, _vp, _vp, _i64, _vp, _vp]),
 }
 

@@ -3,8 +3,8 @@
 Same flag names, defaults and access pattern as the reference (`rl.config.args`, a global
 singleton read at call time; grouped flags appear as `--<prefix>_<name>` and are read as
 `args.<prefix>.<name>`, rl/config.py:38-185).  Defaults cite rl/config.py line numbers.
-Flags of out-of-scope subsystems (distillation, RND, replay, hashing, ...) are
-accepted and ignored with a note, so existing launch lines keep working.
+Flags of out-of-scope subsystems (replay, hashing, ...) are accepted and ignored with a
+note, so existing launch lines keep working.
 """
 import argparse
 import sys
@@ -43,7 +43,7 @@ class _Group:
 
 
 class OptimizerConfig(_Group):  # rl/config.py:249-311
-    EPOCH_DEFAULTS = {"policy_opt": 2, "value_opt": 1, "distil_opt": 2}  # :261-267
+    EPOCH_DEFAULTS = {"policy_opt": 2, "value_opt": 1, "distil_opt": 2, "rnd_opt": 1}  # :261-267
 
     def __init__(self, prefix):
         super().__init__(prefix)
@@ -155,6 +155,22 @@ class TVFConfig(_Group):  # rl/config.py:209-246
     )
 
 
+class RNDConfig(_Group):  # rl/config.py:397-410
+    FIELDS = (
+        ("enabled", bool, False, "Random Network Distillation: intrinsic rewards from a predictor's error"),
+        ("experience_proportion", float, 0.25, "fraction of the rollout the predictor trains on"),
+    )
+
+
+class IRConfig(_Group):  # rl/config.py:445-455
+    FIELDS = (
+        ("propagation", bool, True, "intrinsic returns propagate through the end of an episode"),
+        ("scale", float, 0.3, "intrinsic advantage scale"),
+        ("center", bool, False, "per-batch centring of intrinsic rewards"),
+        ("normalize", bool, True, "normalise intrinsic rewards to unit-variance returns"),
+    )
+
+
 class Config:
     def __init__(self):
         self.policy_opt = OptimizerConfig("policy_opt")
@@ -164,11 +180,17 @@ class Config:
         self.model = ModelConfig("model")
         self.env = EnvConfig("env")
         self.tvf = TVFConfig("tvf")
-        self._groups = (self.policy_opt, self.value_opt, self.distil_opt, self.distil, self.model, self.env, self.tvf)
+        self.rnd_opt = OptimizerConfig("rnd_opt")
+        self.rnd = RNDConfig("rnd")
+        self.ir = IRConfig("ir")
+        # (a flag belongs to the group with the longest matching prefix: rnd_opt_lr is rnd_opt's, rnd_enabled is rnd's)
+        self._groups = (self.policy_opt, self.value_opt, self.distil_opt, self.distil, self.model, self.env, self.tvf,
+                        self.rnd_opt, self.rnd, self.ir)
         # top-level defaults (rl/config.py line numbers)
         self.agents = 256              # :791
         self.n_steps = 256             # :790
         self.gamma = 0.999             # :769
+        self.gamma_int = 0.99          # :770
         self.lambda_policy = 0.95      # :772
         self.lambda_value = 0.95       # :773
         self.ppo_epsilon = 0.2         # :789
@@ -211,7 +233,6 @@ class Config:
         self.workers = -1              # :722
         self.threads = 2               # :723
         self.precision = "medium"      # :764
-        self.use_intrinsic_rewards = False
         self.sync_envs = False
         self.override_reward_normalization_gamma = None  # :780
         self.log_folder = None
@@ -219,6 +240,10 @@ class Config:
 
     # ---- properties the reference derives (rl/config.py:885-901)
     RESOLUTIONS = {"full": (210, 160), "procgen": (64, 64), "nature": (84, 84), "muzero": (96, 96), "half": (105, 80)}
+
+    @property
+    def use_intrinsic_rewards(self):  # rl/config.py:881-883 (the hash bonus is not built)
+        return bool(self.rnd.enabled)
 
     @property
     def batch_size(self):
@@ -240,6 +265,7 @@ class Config:
         a("--agents", type=int, default=self.agents)
         a("--n_steps", type=int, default=self.n_steps)
         a("--gamma", type=float, default=self.gamma)
+        a("--gamma_int", type=float, default=self.gamma_int, help="discount rate for intrinsic rewards")
         a("--lambda_policy", type=float, default=self.lambda_policy)
         a("--lambda_value", type=float, default=self.lambda_value)
         a("--ppo_epsilon", type=float, default=self.ppo_epsilon)
@@ -286,6 +312,7 @@ class Config:
           help="[low|medium|high] (train.py:166-178): high = exact float32 everywhere; low / medium also allow the "
                "split-bf16 launches (3 bf16 MFMAs per product, ~16-bit products) where they exist - the residual blocks of "
                "the IMPALA encoder's 32-channel stacks")
+        # accepted as before; the value follows --rnd_enabled, as the reference's property of that name (rl/config.py:881)
         a("--use_intrinsic_rewards", type=str2bool, nargs="?", const=True, default=False)
         a("--sync_envs", type=str2bool, nargs="?", const=True, default=False)
         a("--override_reward_normalization_gamma", type=float, default=None)
@@ -298,7 +325,7 @@ class Config:
         parser = self.build_parser()
         ns, unknown = parser.parse_known_args(sys.argv[1:] if argv is None else argv)
         for k, v in vars(ns).items():
-            if any(k.startswith(g._prefix + "_") for g in self._groups):
+            if any(k.startswith(g._prefix + "_") for g in self._groups) or k == "use_intrinsic_rewards":
                 continue
             setattr(self, k, v)
         for g in self._groups:
@@ -314,6 +341,8 @@ class Config:
             raise ValueError("Invalid clip_mode.")
         if self.tvf.gamma is None:
             self.tvf.gamma = self.gamma
+        if self.rnd.enabled:
+            assert self.observation_normalization, "RND requires observation normalization"  # rl/config.py:408-410
         # EnvConfig.auto (rl/config.py:563-600)
         if self.env.frame_skip in (None, -1):
             self.env.frame_skip = 4 if self.env.type == "atari" else 1
@@ -343,6 +372,7 @@ class Config:
 
     def flatten(self):
         d = {k: v for k, v in vars(self).items() if not k.startswith("_") and not isinstance(v, _Group)}
+        d["use_intrinsic_rewards"] = self.use_intrinsic_rewards
         for g in self._groups:
             d.update(g.flatten())
         return d

@@ -8,6 +8,9 @@
 //                          data-parallel run can all-reduce them before normalising
 //  * ppo_normalize_f32     (a - mean) / (std + eps) with population std, the batch-level advantage
 //                          normalisation of Runner.train_policy (rl/rollout.py:1887-1900)
+//  * ppo_scale_shift_clip_f32  clip, divide by a float64 scale, subtract a mean: the normalisation of the rollout's
+//                          intrinsic rewards (rl/rollout.py:929, 1165, 1168)
+//  * ppo_axpy_f32          dst += alpha * src (advantage += ir_scale * int_advantage, rl/rollout.py:1227-1228)
 #include "common.h"
 
 namespace ppo {
@@ -139,6 +142,29 @@ __global__ __launch_bounds__(256) void accumulate_kernel(float *__restrict__ dst
     }
 }
 
+// out = (float)((double)clamp(x, -clip, clip) / scale_div - mean), mean = moments[0] / moments[2] (0 without moments)
+__global__ __launch_bounds__(256) void scale_shift_clip_kernel(const float *__restrict__ x, int64_t n, float clip,
+                                                               double scale_div, const double *__restrict__ moments,
+                                                               float *__restrict__ out)
+{
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    float v = x[i];
+    if (clip > 0.0f) v = fminf(fmaxf(v, -clip), clip);
+    const double mean = moments != nullptr ? moments[0] / moments[2] : 0.0;
+    out[i] = (float)((double)v / scale_div - mean);
+}
+
+__global__ __launch_bounds__(256) void axpy_kernel(float *__restrict__ dst, const float *__restrict__ src, float alpha, int64_t n)
+{
+#pragma clang fp contract(off)  // numpy's two roundings: the product is not to be fused into the sum
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) {
+        const float prod = alpha * src[i];
+        dst[i] = dst[i] + prod;
+    }
+}
+
 }  // namespace
 }  // namespace ppo
 
@@ -203,4 +229,24 @@ extern "C" int ppo_accumulate_f32(float *dst, const float *src, int64_t n, void 
     hipLaunchKernelGGL(accumulate_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, as_stream(stream), dst, src,
                        n, vec);
     return check_launch("accumulate_kernel");
+}
+
+extern "C" int ppo_scale_shift_clip_f32(const float *x, int64_t n, float clip, double scale_div, const double *moments,
+                                        float *out, void *stream)
+{
+    using namespace ppo;
+    if (n <= 0 || !x || !out || !(scale_div > 0.0)) return fail(PPO_E_INVALID, "ppo_scale_shift_clip_f32: bad arguments");
+    hipLaunchKernelGGL(scale_shift_clip_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream), x, n, clip,
+                       scale_div, moments, out);
+    return check_launch("scale_shift_clip_kernel");
+}
+
+extern "C" int ppo_axpy_f32(float *dst, const float *src, float alpha, int64_t n, void *stream)
+{
+    using namespace ppo;
+    if (n < 0) return fail(PPO_E_INVALID, "ppo_axpy_f32: n < 0");
+    if (n == 0) return PPO_OK;
+    if (!dst || !src) return fail(PPO_E_INVALID, "ppo_axpy_f32: null pointer");
+    hipLaunchKernelGGL(axpy_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream), dst, src, alpha, n);
+    return check_launch("axpy_kernel");
 }

@@ -13,6 +13,9 @@
 //                             count0 + the number of observations seen, no device round trip needed).
 //  * ppo_obs_normalize_f32    out = clamp((x - mu) / (std + eps), -5, 5), float32 out; bit-identical to the
 //                             torch expression (IEEE subtract / add / divide, no contraction possible).
+//  * ppo_obs_normalize_channel_f32  the same transform for one channel of [B, C, H, W] observations, the rows
+//                             optionally picked through an index: the input of the RND networks (`x[:, -1:]`,
+//                             rl/models.py:723), a quarter of the bytes of the whole transform at C = 4.
 //
 // The reference reduces each batch with float32 torch.mean / torch.var and only then promotes to float64;
 // here the batch is reduced in float64 directly, so the running statistics agree to float32 rounding of one
@@ -100,6 +103,35 @@ __global__ __launch_bounds__(256) void obs_normalize_kernel(const void *__restri
     }
 }
 
+// out[b, p] = normalise(x[row(b), channel, p]), row(b) = index ? index[b] : b;  hw_v = H*W / VEC, plane_v the offset of
+// the channel inside a row and row_v the row length, both in units of VEC elements
+template <int VEC, bool U8>
+__global__ __launch_bounds__(256) void obs_normalize_channel_kernel(const void *__restrict__ x, const int32_t *__restrict__ index,
+                                                                    const float *__restrict__ mu, const float *__restrict__ std,
+                                                                    float eps, float *__restrict__ out, size_t n_vec, int hw_v,
+                                                                    size_t plane_v, size_t row_v)
+{
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_vec; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t b = i / (size_t)hw_v, p = i % (size_t)hw_v;
+        const size_t row = index != nullptr ? (size_t)index[b] : b;
+        const size_t src = row * row_v + plane_v + p, f = plane_v + p;
+        if constexpr (VEC == 4) {
+            float4 v;
+            if constexpr (U8) {
+                const uchar4 r = static_cast<const uchar4 *>(x)[src];
+                v = make_float4((float)r.x / 255.0f, (float)r.y / 255.0f, (float)r.z / 255.0f, (float)r.w / 255.0f);
+            } else {
+                v = static_cast<const float4 *>(x)[src];
+            }
+            const float4 m = reinterpret_cast<const float4 *>(mu)[f], s = reinterpret_cast<const float4 *>(std)[f];
+            reinterpret_cast<float4 *>(out)[i] = make_float4(normalise(v.x, m.x, s.x, eps), normalise(v.y, m.y, s.y, eps),
+                                                             normalise(v.z, m.z, s.z, eps), normalise(v.w, m.w, s.w, eps));
+        } else {
+            out[i] = normalise(prep(x, src, U8), mu[f], std[f], eps);
+        }
+    }
+}
+
 inline int grid_for(size_t n) { return (int)((n + 255) / 256 < 8192 ? (n + 255) / 256 : 8192); }
 
 }  // namespace
@@ -152,4 +184,28 @@ extern "C" int ppo_obs_normalize_f32(const void *x, int is_u8, const float *mu, 
             hipLaunchKernelGGL((obs_normalize_kernel<1, false>), dim3(grid_for(n)), dim3(256), 0, st, x, mu, std, eps, out, n, F);
     }
     return check_launch("obs_normalize_kernel");
+}
+
+extern "C" int ppo_obs_normalize_channel_f32(const void *x, int is_u8, const int32_t *index, const float *mu, const float *std,
+                                             float eps, float *out, int B, int C, int H, int W, int channel, void *stream)
+{
+    using namespace ppo;
+    if (B < 0 || C <= 0 || H <= 0 || W <= 0 || channel < 0 || channel >= C || (long long)C * H * W >= (1ll << 31))
+        return fail(PPO_E_INVALID, "ppo_obs_normalize_channel_f32: bad shape [%d, %d, %d, %d] / channel %d", B, C, H, W, channel);
+    if (B == 0) return PPO_OK;
+    if (!x || !mu || !std || !out) return fail(PPO_E_INVALID, "ppo_obs_normalize_channel_f32: null pointer");
+    const size_t hw = (size_t)H * W, n = (size_t)B * hw;
+    const bool vec = hw % 4 == 0 && aligned(x, is_u8 ? 4 : 16) && aligned(out, 16) && aligned(mu, 16) && aligned(std, 16);
+    const size_t v = vec ? 4 : 1;
+    hipStream_t st = as_stream(stream);
+#define PPO_LAUNCH_CHANNEL(VEC, U8)                                                                                       \
+    hipLaunchKernelGGL((obs_normalize_channel_kernel<VEC, U8>), dim3(grid_for(n / v)), dim3(256), 0, st, x, index, mu, std, \
+                       eps, out, n / v, (int)(hw / v), (size_t)channel * hw / v, (size_t)C * hw / v)
+    if (vec) {
+        if (is_u8) PPO_LAUNCH_CHANNEL(4, true); else PPO_LAUNCH_CHANNEL(4, false);
+    } else {
+        if (is_u8) PPO_LAUNCH_CHANNEL(1, true); else PPO_LAUNCH_CHANNEL(1, false);
+    }
+#undef PPO_LAUNCH_CHANNEL
+    return check_launch("obs_normalize_channel_kernel");
 }

@@ -21,6 +21,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .rnd import RNDNets, init_rnd_parameters  # noqa: F401  (init_rnd_parameters: the RND half of init_parameters)
 
 IN_NONE, IN_RELU, IN_U8 = _lib.PPO_IN_NONE, _lib.PPO_IN_RELU, _lib.PPO_IN_U8
 _ALIGN = 4  # floats: every parameter starts on a 16-byte boundary
@@ -1817,7 +1818,9 @@ class TVFModel:
     """Host mirror of the reference's TVFModel (rl/models.py:511-856): owns `policy_net` and `value_net`
     (the same object for `architecture='single'`, two nets for 'dual'), exposes
     `forward(x, output=..., policy_temperature=...) -> dict` with the reference's routing and key aliasing
-    (:790-821) and a `state_dict` with the reference's `policy_net.` / `value_net.` prefixes."""
+    (:790-821) and a `state_dict` with the reference's `policy_net.` / `value_net.` prefixes.  With `use_rnd` it also owns
+    `prediction_net` / `target_net` (ppo_amd/rnd.py; `rnd_prediction_error`, `forward(include_rnd=True)`, two more
+    `state_dict` prefixes); without it nothing of that exists."""
 
     def __init__(self, encoder: str, encoder_args=None, input_dims=(4, 84, 84), actions: int = 6, device="cuda",
                  architecture: str = "dual", dtype=torch.float32, use_rnd: bool = False, hidden_units: int = 512,
@@ -1829,7 +1832,10 @@ class TVFModel:
         if architecture not in ("single", "dual"):
             raise Exception("Invalid architecture, use [dual|single]")
         if use_rnd:
-            raise NotImplementedError("RND is outside the PPO hot path (DESIGN.md)")
+            assert 'int' in value_head_names, "RND requires int value head."  # rl/models.py:585
+            assert observation_normalization, "rnd requires observation normalization."  # rl/models.py:620
+            if tvf_fixed_head_horizons is not None:
+                raise NotImplementedError("RND together with TVF heads is not built (the reference trains TVF on 'ext' only)")
         if dtype != torch.float32:
             raise ValueError("the reference path is float32 (rl/models.py:31-32)")
         if observation_scaling != "scaled":
@@ -1865,6 +1871,12 @@ class TVFModel:
             self.obs_norm = ObsNormalizer(self.input_dims, self.device, norm_eps=norm_eps,
                                           frozen=freeze_observation_normalization)
             self.policy_net.obs_norm = self.value_net.obs_norm = self.obs_norm
+        self.use_rnd = bool(use_rnd)
+        self.rnd = None
+        if self.use_rnd:
+            # drawn after policy_net / value_net, as the reference's constructor does (rl/models.py:619-622)
+            self.rnd = RNDNets(self.input_dims, self.obs_norm, self.device)
+            self.prediction_net, self.target_net = self.rnd.prediction_net, self.rnd.target_net
 
     def model_size(self, trainable_only: bool = True):
         n = self.policy_net.n_parameters()
@@ -1888,11 +1900,13 @@ class TVFModel:
         if update_normalization and self.obs_norm is not None:
             self.obs_norm.update(x)
         net_args = dict(policy_temperature=policy_temperature, include_features=include_features, **kwargs)
+        if include_rnd:
+            rnd_error = self.rnd_prediction_error(x)  # rl/models.py:786-787
 
         def public(d):
             return {k: (v.clone() if self.architecture == "dual" else v) for k, v in d.items() if not k.startswith("_")}
 
-        result = {}
+        result = {"rnd_error": rnd_error} if include_rnd else {}
         if self.architecture == "single":
             for k, v in public(self.policy_net.forward(x, **net_args)).items():
                 result["policy_" + k] = v
@@ -1934,6 +1948,16 @@ class TVFModel:
             self.obs_norm.update(x)
         return self.obs_norm.apply(x, torch.empty(x.shape, dtype=torch.float32, device=self.device))
 
+    def rnd_prediction_error(self, x, already_normed=False):
+        """rl/models.py:712-738: the prediction error [B] (device) of observations - ndarray or tensor, uint8 or float32;
+        with `already_normed` the float32 output of `perform_normalization`, whose last channel is read as it is."""
+        if not self.use_rnd:
+            raise _lib.PpoAmdError("rnd_prediction_error needs TVFModel(use_rnd=True)")
+        if already_normed:
+            x = torch.as_tensor(x, dtype=torch.float32).to(self.device).contiguous()
+            return self.rnd.prediction_error(x, already_normed=True)
+        return self.rnd.prediction_error(self.prep_for_model(x))
+
     def adjust_value_scale(self, factor: float, process_value=True, process_tvf=True, value_net_only=False):
         """rl/models.py:630-651: scale value predictions by scaling the value / TVF head weights and biases."""
         nets = [self.value_net] if value_net_only else ([self.policy_net] if self.architecture == "single" else
@@ -1950,6 +1974,10 @@ class TVFModel:
         for prefix, net in (("policy_net.", self.policy_net), ("value_net.", self.value_net)):
             for k, v in net.state_dict().items():
                 sd[prefix + k] = v
+        if self.use_rnd:
+            for prefix, net in (("prediction_net.", self.prediction_net), ("target_net.", self.target_net)):
+                for k, v in net.state_dict().items():
+                    sd[prefix + k] = v
         return sd
 
     def load_state_dict(self, sd, strict=True):
@@ -1958,3 +1986,6 @@ class TVFModel:
         if self.architecture == "dual":
             val = {k[len("value_net."):]: v for k, v in sd.items() if k.startswith("value_net.")}
             self.value_net.load_state_dict(val, strict=strict)
+        if self.use_rnd:
+            for prefix, net in (("prediction_net.", self.prediction_net), ("target_net.", self.target_net)):
+                net.load_state_dict({k[len(prefix):]: v for k, v in sd.items() if k.startswith(prefix)}, strict=strict)

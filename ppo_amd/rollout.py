@@ -15,6 +15,11 @@ What changed relative to the reference, and why (MI355X-first):
     minibatch gather, every loss, backward and Adam are HIP kernels (ppo_amd/csrc); minibatches are read
     through an index vector instead of being gathered (only the observations are gathered);
   * statistics are reduced on the device and fetched once per iteration;
+  * Random Network Distillation (`--rnd_enabled`, rl/rollout.py:764-766, 1140-1180, 1804-1841): the prediction error
+    of a group's observations is written into `int_rewards` right behind that group's policy step, with no host read
+    (the reference reads it back every env step); the forward EMS filter and its running variance stay on the host
+    in float64 (N tiny updates, bit-exact with the reference); clipping, scaling, GAE and the advantage sum are
+    device launches; the predictor trains through the same minibatch loop as the other phases;
   * data parallelism: env columns are sharded over ranks (one process per GPU); the only exchanges are one
     RCCL all-reduce of the flat gradient per optimiser step and one of the three advantage moments per
     batch, so an N-GPU run equals a 1-GPU run with N*A envs up to minibatch composition.
@@ -29,6 +34,7 @@ from . import _lib, parallel, value_quality
 from .config import args
 from .models import AdamState
 from .returns import calculate_bootstrapped_returns
+from .running_stats import RunningMeanStd
 
 
 # the synthetic env uploads a group's observations in this many pieces, each as soon as it has been generated (1: one
@@ -38,6 +44,18 @@ UPLOAD_CHUNKS = 2
 
 def _p(t):
     return None if t is None else t.data_ptr()
+
+
+def intrinsic_return_scale(ems_norm, rms, int_rewards, terminals, gamma_int, propagation):
+    """The host half of calculate_intrinsic_returns (rl/rollout.py:1148-1164), expression for expression so that the
+    float64 results carry the reference's bits: the forward exponential-moving-sum filter over the rollout's (clipped)
+    intrinsic rewards [N, A], `rms` (a RunningMeanStd, updated in place) taking in the filter's output after every step.
+    Returns (ems_norm [A] float64, intrinsic_reward_norm_scale)."""
+    for t in range(int_rewards.shape[0]):
+        step_terminals = (not propagation) * terminals[t, :]
+        ems_norm = (1 - step_terminals) * gamma_int * ems_norm + int_rewards[t, :]
+        rms.update(ems_norm.reshape(-1))
+    return ems_norm, (1e-5 + rms.var ** 0.5)
 
 
 class Optimizer:
@@ -85,9 +103,14 @@ class Runner:
         self.state_shape = tuple(model.input_dims)
         self.n_actions = model.actions
         self.VH = self.net.vh
-        if self.VH != 1:
-            raise NotImplementedError("one extrinsic value head on this path (intrinsic rewards are out of scope)")
+        self.rnd = model.rnd if getattr(model, "use_rnd", False) else None
+        if bool(args.rnd.enabled) != (self.rnd is not None):
+            raise ValueError("--rnd_enabled and TVFModel(use_rnd=...) must agree")
+        if self.VH != (2 if self.rnd is not None else 1):
+            raise NotImplementedError("value heads: ('ext',), or ('ext', 'int') with RND")
         self.world, self.rank = parallel.world_size(), parallel.rank()
+        if self.rnd is not None and self.world > 1:
+            raise NotImplementedError("RND under data parallelism is not built (the predictor's gradient is not reduced)")
         N, A, nA, VH, dev = self.N, self.A, self.n_actions, self.VH, self.device
         gaussian = action_dist == "gaussian"
         obs_dtype = torch.uint8 if model.policy_net.encoder_kind in ("impala", "nature") and args.env.type != "mujoco" else torch.float32
@@ -129,6 +152,18 @@ class Runner:
             # value-phase weights: duplicate-head weights times the optional h_weighting (rl/tvf.py:51-62)
             self._tvf_value_weights_dev = torch.as_tensor(self.tvf.value_loss_weights(), device=dev)
             self._ext_estimate = torch.zeros((N + 1, A), dtype=torch.float32, device=dev)
+        # ---- intrinsic rewards (rl/rollout.py:243-246, 279-280)
+        if self.rnd is not None:
+            self.int_rewards = torch.zeros((N, A), dtype=torch.float32, device=dev)
+            self.int_advantage = torch.zeros((N, A), dtype=torch.float32, device=dev)
+            self._head_value = torch.zeros((N + 1, A), dtype=torch.float32, device=dev)  # one head's column, unit stride
+            self._head_returns = torch.zeros((N, A), dtype=torch.float32, device=dev)
+            self._int_rewards_host = torch.zeros((N, A), dtype=torch.float32).pin_memory()
+            self._adv_moments = torch.zeros((2, 3), dtype=torch.float64, device=dev)
+            self._rnd_stats = torch.zeros(_lib.PPO_RND_STATS, dtype=torch.float32, device=dev)
+            self.intrinsic_reward_norm_scale = 1
+            self.intrinsic_returns_rms = RunningMeanStd(shape=())
+            self.ems_norm = np.zeros([A])
         # ---- optimisers (rl/rollout.py:126-141)
         self.policy_optimizer = Optimizer(self.policy_net, args.policy_opt)
         self.value_optimizer = Optimizer(self.value_net, args.value_opt) if self.dual else self.policy_optimizer
@@ -136,6 +171,7 @@ class Runner:
         # whatever the architecture (only `dual` ever steps it; its moment buffers are allocated on first use)
         own_distil = args.distil_opt.epochs > 0 and not args.distil.use_policy_opt
         self.distil_optimizer = Optimizer(self.policy_net, args.distil_opt, AdamState()) if own_distil else None
+        self.rnd_optimizer = Optimizer(self.rnd, args.rnd_opt) if self.rnd is not None else None  # :154-157
         # ---- device scratch
         self._moments = torch.zeros(3, dtype=torch.float64, device=dev)
         self._moments_ws = torch.zeros(self.lib.ppo_moments_workspace_bytes() // 8, dtype=torch.float64, device=dev)
@@ -207,6 +243,18 @@ class Runner:
         return self.returns[:, :, 0]
 
     @property
+    def int_value(self):
+        return self.value[:, :, self.value_heads.index("int")]
+
+    @property
+    def int_returns(self):
+        return self.returns[:, :, self.value_heads.index("int")]
+
+    @property
+    def rnd_lr(self):
+        return self._lr(args.rnd_opt)
+
+    @property
     def prev_obs(self):
         return self.all_obs[:-1]
 
@@ -271,7 +319,7 @@ class Runner:
 
     @property
     def value_heads(self):
-        return ["ext"]
+        return ["ext", "int"] if self.rnd is not None else ["ext"]
 
     @property
     def tvf_horizons(self):
@@ -354,6 +402,10 @@ class Runner:
             rec = self.tvf.tvf_untrimmed_value  # == tvf_value unless --tvf_trimming
             rec[t, lo:hi].copy_(hv[:, val.col_tvf:].view(B, val.K, self.VH))
             rec[t, lo:hi, 0].zero_()  # the first value head (h = 0) is zero by definition (rl/rollout.py:791)
+        if self.rnd is not None and not final:
+            # rl/rollout.py:764-766 without the host read: one channel-normalise launch, the two networks, and the error
+            # straight into this group's columns of row t (the final state's error is never used, :871-878)
+            self.rnd.prediction_error(self.all_obs[t, lo:hi], err=self.int_rewards[t, lo:hi], err_stride=1, tag="r" + tag)
 
     def _log_finished(self, finished, ep_len, ep_score, t=None):
         if finished.any():
@@ -452,6 +504,8 @@ class Runner:
             # the lost steps were real env steps: the vector wrappers' statistics take them in as usual
             env.finish_rollout(self._rewards_host.numpy().copy(), self._dones_host.numpy().copy())
         self._finished_lengths = [[] for _ in range(self.N)]
+        if self.rnd is not None:
+            self.int_rewards.zero_()  # rl/rollout.py:714; every element is written again below
         self._rollout_pipelined(parts, [])
 
     def _rollout_pipelined(self, parts, split_nets=()):
@@ -654,15 +708,79 @@ class Runner:
         if self.tvf is not None:
             self._ext_estimate.copy_(self.tvf.get_tvf_ext_value_estimate(new_gamma=args.gamma))
             value = self._ext_estimate
+        elif self.VH > 1:
+            # the scan wants unit-stride rows: the ext head's column of the [N + 1, A, VH] buffer is copied out, and its
+            # returns are copied back into column 0 (same arithmetic as with one head)
+            self._head_value.copy_(self.ext_value)
+            value = self._head_value
         else:
             value = self.value.view(N + 1, A)
+        ret_out = self.returns if self.VH == 1 else self._head_returns
         self._call("ppo_gae_scan_f32", _p(self.ext_rewards), _p(value), _p(value[N]), _p(self.terminals),
-                   _lib.PPO_TERM_U8, _p(self.advantage), _p(self.returns), N, A, A, float(args.gamma),
+                   _lib.PPO_TERM_U8, _p(self.advantage), _p(ret_out), N, A, A, float(args.gamma),
                    float(args.lambda_policy), float(args.lambda_value), _lib.PPO_SCAN_AUTO)
+        if self.VH > 1:
+            self.ext_returns.copy_(ret_out)
+            value = self.ext_value  # (what the log lines below read; _head_value is reused for the int head)
+        if self.rnd is not None:
+            self._add_intrinsic_advantage()
         if self.tvf is not None:
             self.tvf.tvf_returns[..., 0].copy_(self.tvf.calculate_tvf_returns(value_head="ext"))
         if not args.disable_logging:
             self.log_returns(value)
+
+    def calculate_intrinsic_returns(self):
+        """rl/rollout.py:1140-1180 (and the clip of :929): normalises `int_rewards` in place and fills `int_advantage`
+        and `int_returns`; returns `int_advantage` (device).
+
+        One device->host copy of the N x A rewards; the forward EMS filter and the running variance of its output are
+        N float64 updates on the host, exactly the reference's expressions (a device kernel would save nothing and lose
+        bit-exactness); the scale goes back as a scalar argument.  NumPy >= 2: `int_rewards / scale` with the float64
+        NumPy scalar `scale` is a float64 division (and the mean of --ir_center a float64 mean), which the fixture
+        records and ppo_scale_shift_clip_f32 follows."""
+        N, A = self.N, self.A
+        n = N * A
+        if args.ir.normalize:
+            self._int_rewards_host.copy_(self.int_rewards)
+            rewards = np.clip(self._int_rewards_host.numpy(), -5, 5)  # :929
+            terminals = self.terminals.cpu().numpy() if not args.ir.propagation else np.zeros((N, A), bool)
+            self.ems_norm, self.intrinsic_reward_norm_scale = intrinsic_return_scale(
+                self.ems_norm, self.intrinsic_returns_rms, rewards, terminals, args.gamma_int, args.ir.propagation)
+        self._call("ppo_scale_shift_clip_f32", _p(self.int_rewards), n, 5.0,
+                   float(self.intrinsic_reward_norm_scale) if args.ir.normalize else 1.0, None, _p(self.int_rewards))
+        if args.ir.center:
+            # the mean of the scaled rewards, summed in float64 in a fixed order, then one more pass that subtracts it
+            self._call("ppo_moments_f64", _p(self.int_rewards), n, _p(self._moments), _p(self._moments_ws))
+            self._call("ppo_scale_shift_clip_f32", _p(self.int_rewards), n, 0.0, 1.0, _p(self._moments), _p(self.int_rewards))
+        self._head_value.copy_(self.int_value)
+        value = self._head_value
+        # both lambdas are lambda_policy, so the "returns" output is advantage + V (:1179)
+        self._call("ppo_gae_scan_f32", _p(self.int_rewards), _p(value), _p(value[N]),
+                   None if args.ir.propagation else _p(self.terminals),
+                   _lib.PPO_TERM_NONE if args.ir.propagation else _lib.PPO_TERM_U8, _p(self.int_advantage),
+                   _p(self._head_returns), N, A, A, float(args.gamma_int), float(args.lambda_policy),
+                   float(args.lambda_policy), _lib.PPO_SCAN_AUTO)
+        self.int_returns.copy_(self._head_returns)
+        return self.int_advantage
+
+    def _add_intrinsic_advantage(self):
+        """advantage += ir_scale * int_advantage, and the three log lines (rl/rollout.py:1226-1231)."""
+        n = self.N * self.A
+        logging = not args.disable_logging
+        if logging:
+            self._call("ppo_moments_f64", _p(self.advantage), n, _p(self._adv_moments[0]), _p(self._moments_ws))
+        int_advantage = self.calculate_intrinsic_returns()
+        self._call("ppo_axpy_f32", _p(self.advantage), _p(int_advantage), float(args.ir.scale), n)
+        if logging:
+            self._call("ppo_moments_f64", _p(int_advantage), n, _p(self._adv_moments[1]), _p(self._moments_ws))
+            (_e1, e2, _n), (i1, i2, cnt) = self._adv_moments.cpu().tolist()
+            scale = float(args.ir.scale)
+            mean = scale * i1 / cnt
+            self.log.watch("*adv_int_mean", mean, display_width=0)  # watch_mean_std("*adv_int", ...)
+            self.log.watch("*adv_int_std", math.sqrt(max(scale * scale * i2 / cnt - mean * mean, 0.0)), display_width=0)
+            self.log.watch_mean("adv_ratio", math.sqrt(e2 / (scale * scale * i2)) if i2 > 0 and scale else float("inf"),
+                                display_width=0)
+            self.log.watch_mean("*ir_scale", float(self.intrinsic_reward_norm_scale))
 
     @property
     def reward_scale(self):
@@ -766,27 +884,28 @@ class Runner:
             """Also the exit path of a failed step: the parked hook must come back whatever happened."""
             self.net.grad_ready_hook = self.hook
 
-    def _run_epochs(self, label, optimizer, epochs, mini_batch_size, step_fn, n_stats):
+    def _run_epochs(self, label, optimizer, epochs, mini_batch_size, step_fn, n_stats, rows=None):
         """Permutation minibatching over the rollout (rl/rollout.py:2257-2407): per epoch one host shuffle
         (np.random, as the reference :2319-2320); per minibatch — in micro-batches of at most --max_micro_batch_size
         samples, gradients accumulated, each pass scaled by 1 / micro_batches (:2331-2374) — gather the observations,
         run step_fn(mb_obs, index, loss_scale) -> per-sample stats [n, n_stats], then step the optimiser; the stats
-        are column-summed into one device row per minibatch."""
-        B = self.N * self.A
+        are column-summed into one device row per minibatch.  `rows`: train on the first `rows` samples of the
+        time-major batch only (the RND phase, rl/rollout.py:1830)."""
+        B = self.N * self.A if rows is None else int(rows)
         net = optimizer.net
         mb = parallel.local_minibatch(mini_batch_size)  # the flag is the GLOBAL minibatch (SURVEY.md §8e)
         if B % mb:
             raise ValueError(f"batch {B} is not a multiple of the per-rank minibatch {mb}")
         n_mb = B // mb
         micro, n_micro = self._micro_batches(mb)
-        obs_rows = self.all_obs[:self.N].view(B, -1)
+        obs_rows = self.all_obs[:self.N].view(self.N * self.A, -1)[:B]
         row_bytes = obs_rows.shape[1] * obs_rows.element_size()
         # MLP nets on the fused path read their rows of the whole batch through the permutation and column-sum the
         # statistics in their weight-gradient launch: no gather launch, no column-sum launch
         fused = bool(getattr(net, "mlp_fused", False)) and net.obs_norm is None and self.all_obs.dtype == torch.float32
         # ... and the IMPALA nets read uint8 image rows through the permutation in their first convolution
         in_conv = not fused and hasattr(net, "takes_obs_index") and net.takes_obs_index(self.all_obs)
-        obs_all = self.all_obs[:self.N].view(B, *self.state_shape)
+        obs_all = self.all_obs[:self.N].view(self.N * self.A, *self.state_shape)[:B]
         mb_obs = None if (fused or in_conv) else net._buf("mb_obs", (micro, *self.state_shape), self.all_obs.dtype)
         stat_rows = net._buf(f"stat_rows_{label}", (epochs * n_mb, n_stats))
         norm_rows = net._buf(f"norm_rows_{label}", (epochs * n_mb,))
@@ -890,7 +1009,7 @@ class Runner:
         if use_tvf:
             batch["distil_targets"] = self.tvf.tvf_untrimmed_value[:N, :, :, 0].reshape(B, self.K)
         else:
-            batch["distil_targets"] = self.value[:N].reshape(B)
+            batch["distil_targets"] = self.ext_value[:N].reshape(B)  # (a view with one head, a copy of column 0 with two)
         key = "raw_policy" if self.action_dist == "gaussian" else "log_policy"
         if args.distil.order == "before_policy":
             old = getattr(self, key).view(B, self.n_actions)
@@ -924,8 +1043,22 @@ class Runner:
         self._run_epochs("distil", Optimizer(net, args.distil_opt, opt.state), args.distil_opt.epochs,
                          args.distil_opt.mini_batch_size, step, 4)
 
+    def train_rnd(self):
+        """The predictor's phase (rl/rollout.py:1824-1841): --rnd_opt_epochs epochs of minibatches over the first
+        round(B * --rnd_experience_proportion) samples of the time-major batch, read through the minibatch index."""
+        if args.rnd_opt.epochs == 0:
+            return
+        rows = round(self.N * self.A * args.rnd.experience_proportion)
+        if parallel.local_minibatch(args.rnd_opt.mini_batch_size) < 2:
+            raise ValueError("--rnd_opt_mini_batch_size must be at least 2 (the feature variance over one row is NaN)")
+        self._rnd_stats.zero_()
+
+        def step(obs, idx, loss_scale, **kw):
+            return self.rnd.train_minibatch(obs, idx, loss_scale, stats=self._rnd_stats).view(-1, 1)
+        self._run_epochs("rnd", self.rnd_optimizer, args.rnd_opt.epochs, args.rnd_opt.mini_batch_size, step, 1, rows=rows)
+
     def train(self):
-        """rl/rollout.py:2220-2255: [distil] -> policy -> (dual) value -> [distil]."""
+        """rl/rollout.py:2220-2255: [distil] -> policy -> (dual) value -> [distil] -> [rnd]."""
         self._phase_stats = {}
         if self.wants_distil_update("before_policy"):
             self.train_distil()
@@ -934,6 +1067,8 @@ class Runner:
             self.train_value()
             if self.wants_distil_update("after_policy"):
                 self.train_distil()
+        if self.rnd is not None:
+            self.train_rnd()  # :2252-2253
         self.batch_counter += 1
 
     # ---- the reference's dict-based minibatch API (rl/rollout.py:1331, 1513, 1610, 2257), for callers that
@@ -962,6 +1097,20 @@ class Runner:
                                                vf_coef=args.ppo_vf_coef, tvf_coef=args.tvf.coef, loss_scale=loss_scale)
         total = stats[:, 2].double() * loss_scale
         return {"loss": float(total.mean()), "loss_std": float(total.std())}
+
+    def train_rnd_minibatch(self, data, loss_scale: float = 1.0, **kwargs):
+        """rl/rollout.py:1804-1821: the predictor's gradients for one minibatch of observations."""
+        x = self.model.prep_for_model(data["prev_state"])
+        stats = torch.zeros(_lib.PPO_RND_STATS, dtype=torch.float32, device=self.device)
+        err = self.rnd.train_minibatch(x, None, loss_scale, stats=stats)
+        loss = float(err.double().mean()) * loss_scale
+        _sum, feat_mean, feat_var, feat_max, _n = stats.cpu().tolist()
+        if not args.disable_logging:
+            self.log.watch_mean("loss_rnd", loss / loss_scale)
+            self.log.watch_mean("*feat_mean", feat_mean)
+            self.log.watch_mean("*feat_var", feat_var)
+            self.log.watch_mean("*feat_max", feat_max, display_precision=1)
+        return {"loss": loss}
 
     def train_distil_minibatch(self, data, loss_scale=1.0, **kwargs):
         use_tvf = self.tvf is not None and not args.distil.force_ext
@@ -1061,6 +1210,12 @@ class Runner:
             out.update({"loss_distil_value": s[:, 0].mean(), "loss_distil_policy": s[:, 1].mean(),
                         "loss_distil": s[:, 2].mean(), "distil_mse": s[:, 3].mean(),
                         "grad_distil": float(norm_rows.mean().item())})
+        if "rnd" in self._phase_stats:  # rl/rollout.py:1814-1818; one row of sums for the whole phase (csrc/rnd.hip)
+            stat_rows, norm_rows, mb = self._phase_stats["rnd"]
+            _sum, feat_mean, feat_var, feat_max, calls = self._rnd_stats.cpu().numpy().astype(np.float64)
+            out.update({"loss_rnd": (stat_rows.cpu().numpy().astype(np.float64) / mb).mean(),
+                        "*feat_mean": feat_mean / calls, "*feat_var": feat_var / calls, "*feat_max": feat_max,
+                        "grad_rnd": float(norm_rows.mean().item())})
         if not args.disable_logging:
             for k_, v in out.items():
                 self.log.watch_mean(k_, v)
@@ -1107,8 +1262,16 @@ class Runner:
             data["value_optimizer_state_dict"] = self.value_optimizer.state_dict()    # the policy optimiser (single)
             if self.distil_optimizer is not None:
                 data["distil_optimizer_state_dict"] = self.distil_optimizer.state_dict()
+            if self.rnd_optimizer is not None:
+                data["rnd_optimizer_state_dict"] = self.rnd_optimizer.state_dict()  # rl/rollout.py:416-417
         if self.model.obs_norm is not None:
             data["obs_rms"] = self.model.obs_norm.state_dict()  # rl/rollout.py:438-439
+        if self.rnd is not None:
+            # rl/rollout.py:434-436; the reference pickles the RunningMeanStd object, here its three float64 moments
+            data["ems_norm"] = self.ems_norm.copy()
+            rms = self.intrinsic_returns_rms
+            data["intrinsic_returns_rms"] = {"mean": np.float64(rms.mean), "var": np.float64(rms.var),
+                                             "count": float(rms.count)}
         return checkpoint.save(data, filename, bool(args.checkpoint_compression))
 
     def load_checkpoint(self, checkpoint_path):
@@ -1119,11 +1282,16 @@ class Runner:
         self.model.load_state_dict(cp["model_state_dict"])
         for key, opt in (("policy_optimizer_state_dict", self.policy_optimizer),
                          ("value_optimizer_state_dict", self.value_optimizer if self.dual else None),
-                         ("distil_optimizer_state_dict", self.distil_optimizer)):
+                         ("distil_optimizer_state_dict", self.distil_optimizer),
+                         ("rnd_optimizer_state_dict", self.rnd_optimizer)):
             if opt is not None and key in cp:
                 opt.load_state_dict(cp[key])
         if self.model.obs_norm is not None:
             self.model.obs_norm.load_state_dict(cp["obs_rms"])  # rl/rollout.py:511-513
+        if self.rnd is not None:  # rl/rollout.py:507-509
+            self.ems_norm = np.asarray(cp["ems_norm"], np.float64).copy()
+            rms = cp["intrinsic_returns_rms"]
+            self.intrinsic_returns_rms.restore_state((np.float64(rms["mean"]), np.float64(rms["var"]), rms["count"]))
         self.step = cp["step"]
         self.ep_count = cp.get("ep_count", 0)
         self.batch_counter = cp.get("batch_counter", 0)
