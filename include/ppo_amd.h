@@ -85,9 +85,12 @@ int ppo_bootstrapped_returns_f32(const float *rewards, const void *dones, int do
 
 /* ------------------------------------------------------------------------
  * IMPALA-CNN building blocks (reference: rl/impala.py, rl/models.py:54-99).
- * Activations are NCHW float32, contiguous.  Supported geometries: the layers
- * of the (16, 32, 32)-channel IMPALA stacks on 84x84 (Atari) and 64x64
- * (Procgen) observations; anything else returns PPO_E_INVALID.
+ * Activations are NCHW float32, contiguous.  The entry points of this section
+ * are specialised: their geometries are the layers of the (16, 32, 32)-channel
+ * IMPALA stacks on 84x84 (Atari) and 64x64 (Procgen) observations, anything
+ * else returns PPO_E_INVALID - ask the ppo_conv3x3_*_supported probes first.
+ * Every other geometry has the generic ppo_conv3x3_any_* family further down
+ * (same arguments, same semantics, untuned).
  * ---------------------------------------------------------------------- */
 
 /* input transform fused into the convolution's load */
@@ -105,6 +108,10 @@ int ppo_conv3x3_forward_f32(const void *in, int in_mode, const float *weight, co
                             const float *residual, float *out, int n, int cin, int cout, int h, int w,
                             void *stream);
 
+/* Whether ppo_conv3x3_forward_f32 (and its packed form) has a kernel for this in_mode and geometry: 1 or 0.  Answered by
+ * the dispatcher's own case list in a no-launch mode, as are the three probes below. */
+int ppo_conv3x3_forward_supported(int in_mode, int cin, int cout, int h, int w);
+
 /*
  * Gradient w.r.t. the convolution's (pre-transform) input:
  *   dx[n,i,y,x] = (sum_{o,ky,kx} dy[n,o,y-ky+1,x-kx+1] * weight[o,i,ky,kx]) * [relu_src[n,i,y,x] > 0] + dres[n,i,y,x]
@@ -115,6 +122,7 @@ int ppo_conv3x3_forward_f32(const void *in, int in_mode, const float *weight, co
 int ppo_conv3x3_backward_data_f32(const float *dy, const float *weight, const float *relu_src,
                                   const float *dres, float *dx, int n, int cin, int cout, int h, int w,
                                   void *stream);
+int ppo_conv3x3_backward_data_supported(int cin, int cout, int h, int w);
 
 /*
  * Stack-first convolution fused with the max-pool that follows it (rl/impala.py:104-105):
@@ -124,6 +132,7 @@ int ppo_conv3x3_backward_data_f32(const float *dy, const float *weight, const fl
  */
 int ppo_conv3x3_pool_forward_f32(const void *in, int in_mode, const float *weight, const float *bias, float *out,
                                  uint8_t *argmax, int n, int cin, int cout, int h, int w, void *stream);
+int ppo_conv3x3_pool_forward_supported(int in_mode, int cin, int cout, int h, int w);
 
 /*
  * Pre-packed weights.  Each convolution kernel keeps its MFMA A operand in registers; from the raw [cout,cin,3,3]
@@ -190,6 +199,8 @@ size_t ppo_conv3x3_wgrad_workspace_bytes(int cin, int cout);
 int ppo_conv3x3_backward_weight_f32(const void *in, int in_mode, const float *dy, float *dweight, float *dbias,
                                     void *workspace, size_t workspace_bytes, int n, int cin, int cout, int h,
                                     int w, int accumulate, void *stream);
+/* (also what the *_slabs_f32 and *_slabs_batch*_f32 forms below accept) */
+int ppo_conv3x3_backward_weight_supported(int in_mode, int cin, int cout, int h, int w);
 
 /*
  * The same weight gradient in two steps, for callers that batch the reductions of many layers into one launch
@@ -249,6 +260,34 @@ int ppo_maxpool3x3s2_forward_f32(const float *in, float *out, uint8_t *argmax, i
                                  void *stream);
 int ppo_maxpool3x3s2_backward_f32(const float *dout, const uint8_t *argmax, float *din, int n, int c, int h, int w,
                                   void *stream);
+
+/* ------------------------------------------------------------------------
+ * The same 3x3 / stride 1 / zero-padding 1 convolution at ANY geometry (csrc/conv3x3_any.hip): torch.nn.Conv2d as used
+ * at rl/impala.py:61-62,96 and its autograd, for the observation shapes (--env_resolution, --env_color_mode,
+ * --env_frame_stack, --env_synthetic_shape) and encoder arguments (channels, n_block: rl/models.py:62-80) the
+ * specialised kernels above have no instantiation for.  Implicit GEMMs on the exact-f32 MFMA, padding taps zero by
+ * predicate, f32 accumulation in a fixed order: every launch gives the same bits.  Arguments and semantics are those
+ * of ppo_conv3x3_forward_f32 / ppo_conv3x3_backward_data_f32 / ppo_conv3x3_backward_weight_f32, so a caller swaps
+ * them call for call; the results agree to rounding, not bit for bit (another summation order).  Untuned.
+ *
+ * ppo_conv3x3_any_supported: 1 for 1 <= cin, cout, h, w <= 4096, else 0.  What it rejects - and a batch n < 1, a null
+ *   required pointer or a tensor of 2^30 elements or more - every entry point rejects with PPO_E_INVALID before any
+ *   HIP call.
+ * ppo_conv3x3_any_forward_f32: in_mode PPO_IN_NONE | PPO_IN_RELU | PPO_IN_U8; bias, residual nullable.
+ * ppo_conv3x3_any_backward_data_f32: relu_src, dres nullable (derivative 0 at 0).
+ * ppo_conv3x3_any_backward_weight_f32: the sum over (n, y, x) is cut into slabs whose partial results (dbias among
+ *   them) go to `workspace` - at least ppo_conv3x3_any_wgrad_workspace_bytes(n, cin, cout, h, w) bytes - and are added
+ *   up in ascending order by a second launch; accumulate != 0 adds that sum into dweight / dbias.  dbias nullable.
+ * ---------------------------------------------------------------------- */
+int ppo_conv3x3_any_supported(int cin, int cout, int h, int w);
+int ppo_conv3x3_any_forward_f32(const void *in, int in_mode, const float *weight, const float *bias, const float *residual,
+                                float *out, int n, int cin, int cout, int h, int w, void *stream);
+int ppo_conv3x3_any_backward_data_f32(const float *dy, const float *weight, const float *relu_src, const float *dres,
+                                      float *dx, int n, int cin, int cout, int h, int w, void *stream);
+size_t ppo_conv3x3_any_wgrad_workspace_bytes(int n, int cin, int cout, int h, int w);
+int ppo_conv3x3_any_backward_weight_f32(const void *in, int in_mode, const float *dy, float *dweight, float *dbias,
+                                        void *workspace, size_t workspace_bytes, int n, int cin, int cout, int h, int w,
+                                        int accumulate, void *stream);
 
 /* ------------------------------------------------------------------------
  * Strided convolutions without padding, any geometry (csrc/conv_strided.hip): the layers of the reference's

@@ -70,6 +70,9 @@ thread_local int t_weights_packed = 0;
 // images of the next conv3x3_pool launch are read through this index (ppo_conv3x3_pool_forward_packed_indexed_f32): the
 // minibatch gather of the observations happens in the first convolution's own loads
 thread_local const int32_t *t_in_index = nullptr;
+// the dispatchers below answer "is there a kernel" instead of launching it (the ppo_conv3x3_*_supported probes): one case
+// list serves both, so a probe cannot drift from what a launch accepts
+thread_local int t_probe = 0;
 
 // Packed A operand of a kernel with (kernel-side) CIN input and COUT output channels: for K step s = tap*CINP/4 + cs
 // and channel tile n, lane (l15, g) holds w(co = n*16 + l15, ci = cs*4 + g, tap); four consecutive steps form one
@@ -600,9 +603,11 @@ int dispatch_conv(int cin, int cout, int h, int w_, const void *in, const float 
 // UP: the channel-changing stack-first conv; SAME: everything else.
 #define PPO_CONV_CASE(ALLOWED, CI, CO, HH, WW, TR, MT, NW)                                              \
     if constexpr (ALLOWED) {                                                                           \
-        if (cin == CI && cout == CO && h == HH && w_ == WW)                                            \
+        if (cin == CI && cout == CO && h == HH && w_ == WW) {                                          \
+            if (t_probe) return PPO_OK;                                                                \
             return launch_conv<CI, CO, HH, WW, TR, MT, NW, IN_MODE, TRANSPOSED>(in, w, bias, residual, \
                                                                                  mask_src, out, n, st); \
+        }                                                                                              \
     }
 #ifndef PPO_NW32
 #define PPO_NW32 4
@@ -630,6 +635,7 @@ int dispatch_conv(int cin, int cout, int h, int w_, const void *in, const float 
     PPO_CONV_CASE(SAME, 32, 32, 11, 11, 11, 2, PPO_NW32)   // 121 px = 8 tiles
     PPO_CONV_CASE(SAME, 32, 32, 8, 8, 8, 1, PPO_NW32)      // 64 px = 4 tiles: 1 per wave
 #undef PPO_CONV_CASE
+    if (t_probe) return PPO_E_INVALID;
     return fail(PPO_E_INVALID, "conv3x3: unsupported geometry cin=%d cout=%d h=%d w=%d transposed=%d", cin,
                 cout, h, w_, (int)TRANSPOSED);
 }
@@ -962,12 +968,15 @@ int dispatch_conv_pool(int cin, int cout, int h, int w_, const void *in, const f
 {
 #define PPO_CP_CASE(ALLOWED, CI, CO, HH, WW, PR, MT, NW)                                                   \
     if constexpr (ALLOWED) {                                                                                 \
-        if (cin == CI && cout == CO && h == HH && w_ == WW)                                                  \
+        if (cin == CI && cout == CO && h == HH && w_ == WW) {                                                \
+            if (t_probe) return PPO_OK;                                                                      \
             return launch_conv_pool<CI, CO, HH, WW, PR, MT, NW, IN_MODE>(in, w, bias, out, argmax, n, st);  \
+        }                                                                                                    \
     }
     constexpr bool FLOAT = IN_MODE == IN_NONE;
     if constexpr (IN_MODE == IN_U8) {
-        if (conv1_pool_supported(cin, cout, h, w_, argmax != nullptr))
+        // (a geometry of the list below: a probe finds it there)
+        if (!t_probe && conv1_pool_supported(cin, cout, h, w_, argmax != nullptr))
             return conv1_pool_forward(in, t_in_index, w, t_weights_packed != 0, bias, out, argmax, n, cin, h, w_, st);
     }
 #ifndef PPO_CP_PR84  // 84x84 first layer: pooled rows per item / pixel tiles per wave group
@@ -992,6 +1001,7 @@ int dispatch_conv_pool(int cin, int cout, int h, int w_, const void *in, const f
     PPO_CP_CASE(FLOAT, 32, 32, 21, 21, PPO_CP_PR21, PPO_CP_MT21, PPO_CP_NW21)
     PPO_CP_CASE(FLOAT, 32, 32, 16, 16, 8, 3, 8)   // 17 rows x 16 = 17 tiles
 #undef PPO_CP_CASE
+    if (t_probe) return PPO_E_INVALID;
     return fail(PPO_E_INVALID, "conv3x3_pool: unsupported geometry cin=%d cout=%d h=%d w=%d in_mode=%d", cin, cout, h,
                 w_, IN_MODE);
 }
@@ -1043,6 +1053,43 @@ extern "C" int ppo_conv3x3_pool_forward_f32(const void *in, int in_mode, const f
         case IN_U8: return dispatch_conv_pool<IN_U8>(cin, cout, h, w, in, weight, bias, out, argmax, n, st);
     }
     return fail(PPO_E_INVALID, "ppo_conv3x3_pool_forward_f32: in_mode %d (the stack-first convolution reads raw input)", in_mode);
+}
+
+// The probes: the dispatchers above in no-launch mode.
+extern "C" int ppo_conv3x3_forward_supported(int in_mode, int cin, int cout, int h, int w)
+{
+    using namespace ppo;
+    t_probe = 1;
+    int rc = PPO_E_INVALID;
+    switch (in_mode) {
+        case IN_NONE: rc = dispatch_conv<IN_NONE, false>(cin, cout, h, w, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, nullptr); break;
+        case IN_RELU: rc = dispatch_conv<IN_RELU, false>(cin, cout, h, w, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, nullptr); break;
+        case IN_U8: rc = dispatch_conv<IN_U8, false>(cin, cout, h, w, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, nullptr); break;
+    }
+    t_probe = 0;
+    return rc == PPO_OK ? 1 : 0;
+}
+
+extern "C" int ppo_conv3x3_backward_data_supported(int cin, int cout, int h, int w)
+{
+    using namespace ppo;
+    t_probe = 1;
+    const int rc = dispatch_conv<IN_NONE, true>(cout, cin, h, w, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, nullptr);
+    t_probe = 0;
+    return rc == PPO_OK ? 1 : 0;
+}
+
+extern "C" int ppo_conv3x3_pool_forward_supported(int in_mode, int cin, int cout, int h, int w)
+{
+    using namespace ppo;
+    t_probe = 1;
+    int rc = PPO_E_INVALID;
+    switch (in_mode) {
+        case IN_NONE: rc = dispatch_conv_pool<IN_NONE>(cin, cout, h, w, nullptr, nullptr, nullptr, nullptr, nullptr, 1, nullptr); break;
+        case IN_U8: rc = dispatch_conv_pool<IN_U8>(cin, cout, h, w, nullptr, nullptr, nullptr, nullptr, nullptr, 1, nullptr); break;
+    }
+    t_probe = 0;
+    return rc == PPO_OK ? 1 : 0;
 }
 
 extern "C" int ppo_conv3x3_pool_forward_packed_indexed_f32(const void *in, const int32_t *index, int in_mode, const float *packed,

@@ -209,6 +209,9 @@ __device__ __forceinline__ void wgrad_k_loops(const float *__restrict__ s_x, con
 // workgroups has one ramp and one tail where four launches have four (per-launch constant ~10 us).
 // set by ppo_conv3x3_backward_weight_slabs_pooled_indexed_f32 around its dispatch (see WgradBatch::in_index)
 thread_local const int32_t *t_wgrad_in_index = nullptr;
+// dispatch_wgrad answers "is there a kernel" instead of launching it (ppo_conv3x3_backward_weight_supported): one case
+// list serves both
+thread_local int t_wgrad_probe = 0;
 constexpr int kWgradBatch = 5;  // a stack's four block convolutions + the next stack's first convolution (same geometry)
 struct WgradBatch {
     const void *in[kWgradBatch];
@@ -665,9 +668,11 @@ int dispatch_wgrad(int cin, int cout, int h, int w_, const void *in, const float
                     cout, h, w_, IN_MODE);
 #define PPO_WGRAD_CASE(ALLOWED, CI, CO, HH, WW, TR)                                                  \
     if constexpr (ALLOWED) {                                                                         \
-        if (cin == CI && cout == CO && h == HH && w_ == WW)                                          \
+        if (cin == CI && cout == CO && h == HH && w_ == WW) {                                        \
+            if (t_wgrad_probe) return PPO_OK;                                                        \
             return launch_wgrad<CI, CO, HH, WW, TR, IN_MODE>(in, dy, dw, db, ws, ws_bytes, n, accumulate, st, n_slabs_out, \
                                                              more, count);                                   \
+        }                                                                                            \
     }
     constexpr bool FIRST = IN_MODE != IN_RELU;
     constexpr bool UP = IN_MODE == IN_NONE;
@@ -687,6 +692,7 @@ int dispatch_wgrad(int cin, int cout, int h, int w_, const void *in, const float
     PPO_WGRAD_CASE(SAME, 32, 32, 11, 11, 11)
     PPO_WGRAD_CASE(SAME, 32, 32, 8, 8, 8)
 #undef PPO_WGRAD_CASE
+    if (t_wgrad_probe) return PPO_E_INVALID;
     return fail(PPO_E_INVALID, "conv3x3_wgrad: unsupported geometry cin=%d cout=%d h=%d w=%d in_mode=%d", cin, cout,
                 h, w_, IN_MODE);
 }
@@ -716,6 +722,21 @@ extern "C" int ppo_conv3x3_backward_weight_f32(const void *in, int in_mode, cons
         case IN_U8: return dispatch_wgrad<IN_U8>(cin, cout, h, w, in, dy, dweight, dbias, ws, workspace_bytes, n, accumulate, st);
     }
     return fail(PPO_E_INVALID, "ppo_conv3x3_backward_weight_f32: unknown in_mode %d", in_mode);
+}
+
+// The probe: dispatch_wgrad in no-launch mode (the plain, slab and batched forms share its case list).
+extern "C" int ppo_conv3x3_backward_weight_supported(int in_mode, int cin, int cout, int h, int w)
+{
+    using namespace ppo;
+    t_wgrad_probe = 1;
+    int rc = PPO_E_INVALID;
+    switch (in_mode) {
+        case IN_NONE: rc = dispatch_wgrad<IN_NONE>(cin, cout, h, w, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 1, 0, nullptr); break;
+        case IN_RELU: rc = dispatch_wgrad<IN_RELU>(cin, cout, h, w, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 1, 0, nullptr); break;
+        case IN_U8: rc = dispatch_wgrad<IN_U8>(cin, cout, h, w, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 1, 0, nullptr); break;
+    }
+    t_wgrad_probe = 0;
+    return rc == PPO_OK ? 1 : 0;
 }
 
 extern "C" int ppo_conv3x3_backward_weight_slabs_f32(const void *in, int in_mode, const float *dy, void *workspace,

@@ -441,6 +441,7 @@ class DualHeadNet:
         self._split_ws = {}  # workspaces of the two-workgroups-per-image chain launch
         self._plans = {}   # (tag, batch, dtype) -> recorded inference launch list
         self.use_plans = True  # False: every inference launch goes through _call (bench.py's per-kernel table brackets it)
+        self._find_generic_convs()
         self._build_packed_weights()
         self._build_split_bf16(precision)
         self._build_mlp_fused()
@@ -507,7 +508,8 @@ class DualHeadNet:
         jobs = []
         nbytes = int(self.lib.ppo_impala_stack_tail_bf16x3_packed_bytes())
         for si, (_cin, cout, _h, _w, ho, wo) in enumerate(self.spec.stacks):
-            if not self.lib.ppo_impala_stack_tail_bf16x3_supported(cout, ho, wo):
+            if not self.lib.ppo_impala_stack_tail_bf16x3_supported(cout, ho, wo) \
+                    or f"encoder.stacks.{si}.blocks.0.conv0" in self._generic:
                 continue
             for tr, order in ((0, ((0, 0), (0, 1), (1, 0), (1, 1))), (1, ((1, 1), (1, 0), (0, 1), (0, 0)))):
                 buf = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
@@ -527,6 +529,8 @@ class DualHeadNet:
             if not (self.split_bf16 and SPLIT_CONV and si > 0 and cin in (16, 32) and cout in (16, 32)):
                 continue
             wname = f"encoder.stacks.{si}.firstconv"
+            if wname in self._generic:
+                continue
             nb = int(self.lib.ppo_conv3x3_bf16x3_packed_bytes(cin, cout))
             for tr, (ci_op, co_op) in ((0, (cin, cout)), (1, (cout, cin))):
                 if not self.lib.ppo_conv3x3_bf16x3_supported(ci_op, co_op, h, w):
@@ -624,6 +628,47 @@ class DualHeadNet:
         names = ["log_std"] + [n for n in self._state_order if n != "log_std"]
         return OrderedDict((n, self.params[n]) for n in names)
 
+    # ------------------------------------------------------------------ convolutions without a specialised kernel
+    def _find_generic_convs(self):
+        """`generic_convs`: the IMPALA convolutions, by parameter name, that the specialised kernels (csrc/conv3x3.hip,
+        csrc/conv3x3_wgrad.hip: the layers of the (16, 32, 32) stacks on 84x84 and 64x64 observations) have no
+        instantiation for - another --env_resolution / --env_color_mode / --env_frame_stack / --env_synthetic_shape, or
+        other `channels` / `n_block` encoder arguments.  Their forward, backward-data and weight-gradient launches are
+        the generic ppo_conv3x3_any_* ones, in exact float32 whatever `precision`.  Decided per convolution, by asking
+        the specialised dispatchers' own probes: a net keeps every specialised and fused launch its other layers
+        qualify for (a (12, 84, 84) net moves its first convolution only).  A generic convolution has no packed
+        weights, which is also what keeps the fused stack / block launches - all of them read packed weights - off it."""
+        self.generic_convs, self._probes = [], {}
+        if self.encoder_kind == "impala":
+            lib, sp = self.lib, self.spec
+
+            def specialised(modes, cin, cout, h, w, data_grad):
+                return all(lib.ppo_conv3x3_forward_supported(m, cin, cout, h, w)
+                           and lib.ppo_conv3x3_backward_weight_supported(m, cin, cout, h, w) for m in modes) \
+                    and (not data_grad or lib.ppo_conv3x3_backward_data_supported(cin, cout, h, w))
+
+            for si, (cin, cout, h, w, ho, wo) in enumerate(sp.stacks):
+                # the observations arrive as uint8 or (normalised, or float environments) as float32; nothing
+                # back-propagates into them
+                if not specialised((IN_U8, IN_NONE) if si == 0 else (IN_NONE,), cin, cout, h, w, si > 0):
+                    self.generic_convs.append(f"encoder.stacks.{si}.firstconv")
+                    if not lib.ppo_conv3x3_any_supported(cin, cout, h, w):
+                        raise _lib.PpoAmdError(f"no 3x3 convolution kernel for {cin}->{cout} on {h}x{w}")
+                if not specialised((IN_RELU,), cout, cout, ho, wo, True):
+                    self.generic_convs += [f"encoder.stacks.{si}.blocks.{bi}.conv{ci}" for bi in range(sp.n_block)
+                                           for ci in range(2)]
+                    if not lib.ppo_conv3x3_any_supported(cout, cout, ho, wo):
+                        raise _lib.PpoAmdError(f"no 3x3 convolution kernel for {cout}->{cout} on {ho}x{wo}")
+        self._generic = frozenset(self.generic_convs)
+
+    def _probe(self, fn_name, *args) -> bool:
+        """A *_supported probe of the library, asked once per argument list."""
+        key = (fn_name, args)
+        ok = self._probes.get(key)
+        if ok is None:
+            ok = self._probes[key] = bool(getattr(self.lib, fn_name)(*args))
+        return ok
+
     # ------------------------------------------------------------------ pre-packed convolution weights
     def _build_packed_weights(self):
         """One buffer with, per convolution, the forward kernels' A operand and the backward-data kernels' (flipped,
@@ -633,8 +678,8 @@ class DualHeadNet:
             return
         jobs, total = [], 0
         for name, w in self.params.items():
-            if not (name.startswith("encoder.stacks.") and name.endswith(".weight")):
-                continue
+            if not (name.startswith("encoder.stacks.") and name.endswith(".weight")) or name[:-len(".weight")] in self._generic:
+                continue  # (the generic kernels read the raw tensor)
             cout, cin = int(w.shape[0]), int(w.shape[1])
             for transposed in (0, 1):
                 if transposed and name == "encoder.stacks.0.firstconv.weight":
@@ -642,6 +687,8 @@ class DualHeadNet:
                 n = int(self.lib.ppo_conv3x3_packed_floats(cin, cout, transposed))
                 jobs.append((name[:-len(".weight")], transposed, cin, cout, total, n))
                 total += n
+        if not jobs:
+            return
         self._packed = torch.zeros(total, dtype=torch.float32, device=self.device)
         table = (_lib.PackJob * len(jobs))()
         for k, (wname, transposed, cin, cout, off, n) in enumerate(jobs):
@@ -752,6 +799,10 @@ class DualHeadNet:
 
     # ------------------------------------------------------------------ forward
     def _conv(self, x, mode, wname, out, residual, n, cin, cout, h, w):
+        if wname in self._generic:
+            self._call("ppo_conv3x3_any_forward_f32", _p(x), mode, _p(self.params[wname + ".weight"]),
+                       _p(self.params[wname + ".bias"]), _p(residual), _p(out), n, cin, cout, h, w)
+            return
         pk = self._pk.get((wname, 0))
         if pk is not None:
             self._call("ppo_conv3x3_forward_packed_f32", _p(x), mode, _p(pk), _p(self.params[wname + ".bias"]),
@@ -1029,7 +1080,8 @@ class DualHeadNet:
                     self._call("ppo_conv3x3_bf16x3", _p(cur), int(cur_mode == IN_RELU), _p(self._pk16[(wname, 0)]),
                                _p(self.params[wname + ".bias"]), _p(c), B, cin, cout, h, w)
                     self._call("ppo_maxpool3x3s2_forward_f32", _p(c), _p(p), _p(idx), B, cout, h, w)
-            elif FUSE_POOL_STACKS >> si & 1:
+            elif FUSE_POOL_STACKS >> si & 1 and wname not in self._generic \
+                    and self._probe("ppo_conv3x3_pool_forward_supported", int(cur_mode), cin, cout, h, w):
                 # stack-first convolution + max-pool, fused: the pre-pool map never reaches HBM
                 pk = self._pk.get((wname, 0))
                 if si == 0 and index is not None:
@@ -1300,6 +1352,13 @@ class DualHeadNet:
 
         def wgrad(x, mode, dy, wname, n, cin, cout, hh, ww, argmax=None):
             """argmax given: dy is the POOLED gradient and the kernel forms max-pool backward itself."""
+            if wname in self._generic:
+                # no specialised kernel: the generic one, slabs reduced by a launch of its own straight into self.grad
+                nbytes = int(lib.ppo_conv3x3_any_wgrad_workspace_bytes(n, cin, cout, hh, ww))
+                ws = self._ws("wgrad_ws_" + wname, nbytes)
+                self._call("ppo_conv3x3_any_backward_weight_f32", _p(x), mode, _p(dy), _p(self.grads[wname + ".weight"]),
+                           _p(self.grads[wname + ".bias"]), _p(ws), nbytes, n, cin, cout, hh, ww, 0)
+                return
             nbytes = lib.ppo_conv3x3_wgrad_workspace_bytes(cin, cout)
             ws = self._ws("wgrad_ws_" + wname, nbytes)  # per layer: the slabs live until the batched reduction
             n_slabs = ctypes.c_int(0)
@@ -1328,7 +1387,7 @@ class DualHeadNet:
 
         def wgrad_blocks(problems, n, c, hh, ww):
             """Weight gradients of a stack's block convolutions, problems = [(x, dy, wname)] (all IN_RELU, c -> c)."""
-            if not WGRAD_BATCH_LAUNCH or len(problems) > 4:
+            if not WGRAD_BATCH_LAUNCH or len(problems) > 4 or problems[0][2] in self._generic:
                 flush_carry()
                 for x, dy, wname in problems:
                     wgrad(x, IN_RELU, dy, wname, n, c, c, hh, ww)
@@ -1456,13 +1515,15 @@ class DualHeadNet:
             # max-pool backward, then the stack's first convolution
             x_in = acts[f"in{si}"]
             mode = IN_NONE if si > 0 else (IN_U8 if x_in.dtype == torch.uint8 else IN_NONE)
-            if si == 0 and WGRAD_POOLED_DY and lib.ppo_conv3x3_backward_weight_pooled_supported(cin, cout, hh, ww):
+            if si == 0 and WGRAD_POOLED_DY and f"encoder.stacks.{si}.firstconv" not in self._generic \
+                    and lib.ppo_conv3x3_backward_weight_pooled_supported(cin, cout, hh, ww):
                 # nothing else reads this stack's pre-pool gradient: the weight-gradient kernel forms it band by band
                 wgrad(x_in, mode, g, f"encoder.stacks.{si}.firstconv", B, cin, cout, hh, ww, argmax=acts[f"idx{si}"])
                 continue
             dc = self._buf(f"g{si}_dc", (B, cout, hh, ww))
             self._call("ppo_maxpool3x3s2_backward_f32", _p(g), _p(acts[f"idx{si}"]), _p(dc), B, cout, hh, ww)
             if WGRAD_RIDE and WGRAD_BATCH_LAUNCH and si > 0 and cin == cout \
+                    and f"encoder.stacks.{si}.firstconv" not in self._generic \
                     and mode == IN_NONE and sp.n_block == 2 and sp.stacks[si - 1][1] == cin \
                     and tuple(sp.stacks[si - 1][4:6]) == (hh, ww):
                 carry.append((x_in, dc, f"encoder.stacks.{si}.firstconv", B, cin, hh, ww))  # rides in the next stack's launch
@@ -1539,6 +1600,8 @@ class DualHeadNet:
         return cached
 
     def _bwd_data_fn(self, wname):
+        if wname in self._generic:
+            return "ppo_conv3x3_any_backward_data_f32"
         return "ppo_conv3x3_backward_data_packed_f32" if (wname, 1) in self._pk else "ppo_conv3x3_backward_data_f32"
 
     def _bwd_w(self, wname):
@@ -1549,8 +1612,10 @@ class DualHeadNet:
         """Whether a training minibatch can read its observations out of the whole batch through the permutation
         (ppo_conv3x3_pool_forward_packed_indexed_f32 + the indexed first-layer weight gradient) instead of from a
         gathered copy: uint8 images into the fused first convolution + max-pool, the pooled-gradient weight-gradient form.
-        IMPALA only: the nature and mlp op-by-op paths take the gathered minibatch."""
-        if self.encoder_kind != "impala" or obs.dtype != torch.uint8 or self.obs_norm is not None or not GATHER_IN_CONV:
+        IMPALA only, and only where the first convolution has its specialised kernels (the generic ones take the gathered
+        minibatch): the nature and mlp op-by-op paths take the gathered minibatch."""
+        if self.encoder_kind != "impala" or "encoder.stacks.0.firstconv" in self._generic or obs.dtype != torch.uint8 \
+                or self.obs_norm is not None or not GATHER_IN_CONV:
             return False
         cin, cout, h, w, _ho, _wo = self.spec.stacks[0]
         return bool(FUSE_POOL_STACKS & 1) and self._pk.get(("encoder.stacks.0.firstconv", 0)) is not None \
