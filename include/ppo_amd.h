@@ -715,6 +715,52 @@ int ppo_rnd_error_f32(const float *pred, const float *target, int B, int F, floa
                       float grad_scale, float *stats, void *stream);
 
 /* ------------------------------------------------------------------------
+ * State hashing (csrc/state_hash.hip): exploration counts and the count-based novelty bonus.
+ *
+ * ppo_state_hash_i32 - LinearStateHasher.forward on the input generate_hashes prepares (rl/hash.py:22-54,
+ *   rl/rollout.py:652-699): out[b] = sum_i [weight[i] . x_b + bias[i] > 0] * 2^i.
+ *   obs      [B, C, H, W] uint8, rows contiguous (stride C*H*W): a row slice of the rollout's observation buffer
+ *   planes   1: channel 0 alone is hashed (the reference's `atari` filter, :665-666), D = H*W; C: every element in
+ *            memory order, D = C*H*W
+ *   quantize o <- (o / quantize) * quantize (:670-671); 0 and 1 leave o as it is
+ *   mode     PPO_HASH_RAW x = o; _RAW_CENTERED x = o - 128; _NORMED x = clamp((o/255 - mu) / (std + eps), -5, 5), the
+ *            float32 expression of ppo_obs_normalize_f32; _NORMED_OFFSET that plus 3.0f (:674-684).  mu / std: the
+ *            normaliser's float32 constants [C*H*W] (normed modes; else nullable)
+ *   weight   [bits, D] float32, bias [bits] float32, 1 <= bits <= 24
+ *   Each x is formed in float32, x and w are promoted to float64 and w*x (exact in float64) is summed in float64 in an
+ *   order that depends on D alone: a row's hash is the same bits for every B, every split of the rows into calls and
+ *   every alignment, and the bit is the sign of the true sum whenever |sum| > (D + 2) 2^-53 (sum |w x| + |bias|).
+ *   (The reference's float32 BLAS sum gives hashes that differ between CPU and GPU.)
+ *
+ * ppo_hash_counts_update_f64 - rl/rollout.py:758-762 for the N recorded steps of a rollout, in its order:
+ *   for t < N: recent[:] *= decay; for a < A: global[hashes[t,a]] += 1, recent[hashes[t,a]] += 1.
+ *   hashes [N, A] int32; global / recent [n_bins] float64.  Bit-identical to the float64 host loop (N separate rounded
+ *   multiplications, every `+ 1` rounded on its own).  An entry outside [0, n_bins) is skipped.
+ *
+ * ppo_hash_bonus_f32 - rl/rollout.py:898-924: int_rewards[i] = (float)((double)int_rewards[i] + bonus * g(recent[hashes[i]])),
+ *   g = 1/c (HYPERBOLIC), 1/(c*c) (QUADRATIC), c < threshold ? 1 : -1 (BINARY); the product and the sum are rounded
+ *   separately.  Entries outside [0, n_bins) are left alone.
+ *
+ * ppo_hash_count_stats - rl/rollout.py:1248-1250: out[0] = count_nonzero(global), out[1] = count_nonzero(recent.astype(int))
+ *   (= the bins >= 1); out: device int64[2], overwritten.
+ * ---------------------------------------------------------------------- */
+#define PPO_HASH_RAW 0
+#define PPO_HASH_RAW_CENTERED 1
+#define PPO_HASH_NORMED 2
+#define PPO_HASH_NORMED_OFFSET 3
+#define PPO_HASH_BONUS_HYPERBOLIC 0
+#define PPO_HASH_BONUS_QUADRATIC 1
+#define PPO_HASH_BONUS_BINARY 2
+int ppo_state_hash_i32(const uint8_t *obs, int B, int C, int H, int W, int planes, int quantize, int mode, const float *mu,
+                       const float *std, float eps, const float *weight, const float *bias, int bits, int32_t *out,
+                       void *stream);
+int ppo_hash_counts_update_f64(const int32_t *hashes, int N, int A, double decay, double *global_counts,
+                               double *recent_counts, int64_t n_bins, void *stream);
+int ppo_hash_bonus_f32(const int32_t *hashes, int64_t n, const double *recent_counts, int64_t n_bins, int method,
+                       double threshold, double bonus, float *int_rewards, void *stream);
+int ppo_hash_count_stats(const double *global_counts, const double *recent_counts, int64_t n_bins, int64_t *out, void *stream);
+
+/* ------------------------------------------------------------------------
  * Synthetic vectorised environment (HOST pointers; runs on host threads).
  * The benchmark workload of SURVEY.md §8(d): obs uint8 i.i.d. uniform, reward ~ N(0,1),
  * done ~ Bernoulli(p_done), auto-reset; stands where the reference has the

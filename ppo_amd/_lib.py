@@ -19,6 +19,8 @@ PPO_TERM_NONE, PPO_TERM_U8, PPO_TERM_F32 = 0, 1, 2
 PPO_SCAN_AUTO, PPO_SCAN_COLUMNS, PPO_SCAN_TILES = 0, 1, 2
 PPO_IN_NONE, PPO_IN_RELU, PPO_IN_U8 = 0, 1, 2
 PPO_RND_STATS = 5
+PPO_HASH_RAW, PPO_HASH_RAW_CENTERED, PPO_HASH_NORMED, PPO_HASH_NORMED_OFFSET = 0, 1, 2, 3
+PPO_HASH_BONUS_HYPERBOLIC, PPO_HASH_BONUS_QUADRATIC, PPO_HASH_BONUS_BINARY = 0, 1, 2
 
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
@@ -155,6 +157,10 @@ SIGNATURES = {
     "ppo_scale_shift_clip_f32": (_i, [_vp, _i64, _f, _d, _vp, _vp, _vp]),
     "ppo_axpy_f32": (_i, [_vp, _vp, _f, _i64, _vp]),
     "ppo_adam_step_scatter_f32": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _d, _d, _d, _d, _f, _f, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "ppo_state_hash_i32": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _f, _vp, _vp, _i, _vp, _vp]),
+    "ppo_hash_counts_update_f64": (_i, [_vp, _i, _i, _d, _vp, _vp, _i64, _vp]),
+    "ppo_hash_bonus_f32": (_i, [_vp, _i64, _vp, _i64, _i, _d, _d, _vp, _vp]),
+    "ppo_hash_count_stats": (_i, [_vp, _vp, _i64, _vp, _vp]),
 }
 
 class PackJob(ctypes.Structure):

@@ -3,8 +3,9 @@
 Same flag names, defaults and access pattern as the reference (`rl.config.args`, a global
 singleton read at call time; grouped flags appear as `--<prefix>_<name>` and are read as
 `args.<prefix>.<name>`, rl/config.py:38-185).  Defaults cite rl/config.py line numbers.
-Flags of out-of-scope subsystems (replay, hashing, ...) are accepted and ignored with a
-note, so existing launch lines keep working.
+Flags of out-of-scope subsystems (replay, ...) are accepted and ignored with a
+note, so existing launch lines keep working.  The `hash` group is registered only on a launch line that enables hashing
+(`--hash_enabled[=True]`): every other line parses exactly as it did before state hashing was built.
 """
 import argparse
 import sys
@@ -162,6 +163,41 @@ class RNDConfig(_Group):  # rl/config.py:397-410
     )
 
 
+class HashConfig(_Group):  # rl/config.py:412-429
+    FIELDS = (
+        ("enabled", bool, False, "state hashing: counts of visited (hashed) states"),
+        ("bits", int, 16, "bits of the hash; the two count tables hold 2^bits float64 each"),
+        ("bonus", float, 0.0, "intrinsic reward bonus for novel hashed states"),
+        ("method", str, "linear", "[linear]  (conv is not built)"),
+        ("input", str, "raw", "[raw|raw_centered|normed|normed_offset]"),
+        ("bonus_method", str, "hyperbolic", "[hyperbolic|quadratic|binary]"),
+        ("rescale", int, 1, "downscale factor of the hashed frame (only 1 is built)"),
+        ("quantize", float, 1, "quantisation step of the hashed bytes (integers only)"),
+        ("bias", float, 0.0, "range of the hasher's uniform bias"),
+        ("decay", float, 0.99, "per-step decay of the recent counts"),
+    )
+
+
+def hashing_enabled_on(argv):
+    """Whether a launch line enables state hashing somewhere: a `--hash_enabled`, `--hash_enabled=<true>` or
+    `--hash_enabled <true>` on it.  (A later `--hash_enabled=False` on such a line is then the parser's to resolve: the
+    last one wins, and verify() refuses a bonus that is left without hashing.)"""
+    for i, a in enumerate(argv):
+        value = None
+        if a == "--hash_enabled":
+            nxt = argv[i + 1] if i + 1 < len(argv) else None
+            value = "true" if nxt is None or nxt.startswith("--") else nxt
+        elif a.startswith("--hash_enabled="):
+            value = a.split("=", 1)[1]
+        if value is not None:
+            try:
+                if str2bool(value):
+                    return True
+            except argparse.ArgumentTypeError:
+                return True  # the parser reports the bad value
+    return False
+
+
 class IRConfig(_Group):  # rl/config.py:445-455
     FIELDS = (
         ("propagation", bool, True, "intrinsic returns propagate through the end of an episode"),
@@ -183,6 +219,7 @@ class Config:
         self.rnd_opt = OptimizerConfig("rnd_opt")
         self.rnd = RNDConfig("rnd")
         self.ir = IRConfig("ir")
+        self.hash = HashConfig("hash")  # not in _groups: registered per launch line (setup)
         # (a flag belongs to the group with the longest matching prefix: rnd_opt_lr is rnd_opt's, rnd_enabled is rnd's)
         self._groups = (self.policy_opt, self.value_opt, self.distil_opt, self.distil, self.model, self.env, self.tvf,
                         self.rnd_opt, self.rnd, self.ir)
@@ -242,8 +279,8 @@ class Config:
     RESOLUTIONS = {"full": (210, 160), "procgen": (64, 64), "nature": (84, 84), "muzero": (96, 96), "half": (105, 80)}
 
     @property
-    def use_intrinsic_rewards(self):  # rl/config.py:881-883 (the hash bonus is not built)
-        return bool(self.rnd.enabled)
+    def use_intrinsic_rewards(self):  # rl/config.py:881-883 (a bonus without --hash_enabled cannot be set: verify())
+        return bool(self.rnd.enabled) or bool(self.hash.enabled and self.hash.bonus != 0)
 
     @property
     def batch_size(self):
@@ -322,13 +359,20 @@ class Config:
 
     def setup(self, argv=None):
         """Parse argv (default sys.argv[1:]) like rl.config.args.setup() (rl/config.py:709-801)."""
+        argv = list(sys.argv[1:] if argv is None else argv)
         parser = self.build_parser()
-        ns, unknown = parser.parse_known_args(sys.argv[1:] if argv is None else argv)
+        # the hash flags exist only on a line that enables hashing; on any other line they are unknown flags as before
+        # (ignored with a note, in command-line order) and args.hash holds the defaults
+        self.hash = HashConfig("hash")
+        groups = self._groups + ((self.hash,) if hashing_enabled_on(argv) else ())
+        if len(groups) > len(self._groups):
+            self.hash.add(parser)
+        ns, unknown = parser.parse_known_args(argv)
         for k, v in vars(ns).items():
-            if any(k.startswith(g._prefix + "_") for g in self._groups) or k == "use_intrinsic_rewards":
+            if any(k.startswith(g._prefix + "_") for g in groups) or k == "use_intrinsic_rewards":
                 continue
             setattr(self, k, v)
-        for g in self._groups:
+        for g in groups:
             g.update(ns)
         self._ignored = [u for u in unknown if u.startswith("--")]
         self.verify()
@@ -343,6 +387,24 @@ class Config:
             self.tvf.gamma = self.gamma
         if self.rnd.enabled:
             assert self.observation_normalization, "RND requires observation normalization"  # rl/config.py:408-410
+        if self.hash.bonus != 0:
+            assert self.hash.enabled, "use_hashing must be enabled."  # rl/config.py:871-872
+        if self.hash.enabled:
+            if self.hash.method == "conv":
+                raise NotImplementedError("--hash_method=conv is not built: its 1x1 squeeze layer is drawn from the global "
+                                          "RNG, not the seeded generator, so its tables do not survive a restart")
+            if self.hash.method != "linear":
+                raise ValueError(f"Invalid hashing method '{self.hash.method}' (linear)")
+            if self.hash.rescale != 1:
+                raise NotImplementedError("--hash_rescale != 1 is not built (it needs OpenCV's INTER_AREA rounding)")
+            if self.hash.quantize != int(self.hash.quantize) or not 0 <= self.hash.quantize <= 255:
+                raise NotImplementedError("--hash_quantize must be an integer in [0, 255]: the hashed bytes are uint8")
+            if self.hash.input not in ("raw", "raw_centered", "normed", "normed_offset"):
+                raise ValueError(f"Invalid hash_input {self.hash.input}")
+            if self.hash.bonus_method not in ("hyperbolic", "quadratic", "binary"):
+                raise ValueError(f"Invalid hash_bonus_method {self.hash.bonus_method}")
+            if not 1 <= self.hash.bits <= 24:
+                raise ValueError(f"--hash_bits={self.hash.bits}: 1 to 24 bits (two float64 tables of 2^bits entries)")
         # EnvConfig.auto (rl/config.py:563-600)
         if self.env.frame_skip in (None, -1):
             self.env.frame_skip = 4 if self.env.type == "atari" else 1
@@ -373,7 +435,7 @@ class Config:
     def flatten(self):
         d = {k: v for k, v in vars(self).items() if not k.startswith("_") and not isinstance(v, _Group)}
         d["use_intrinsic_rewards"] = self.use_intrinsic_rewards
-        for g in self._groups:
+        for g in self._groups + ((self.hash,) if self.hash.enabled else ()):
             d.update(g.flatten())
         return d
 

@@ -20,6 +20,11 @@ What changed relative to the reference, and why (MI355X-first):
     (the reference reads it back every env step); the forward EMS filter and its running variance stay on the host
     in float64 (N tiny updates, bit-exact with the reference); clipping, scaling, GAE and the advantage sum are
     device launches; the predictor trains through the same minibatch loop as the other phases;
+  * state hashing (`--hash_enabled`, rl/rollout.py:652-699, 755-762, 895-924): a group's observations are hashed where
+    they lie, one launch behind its policy step that writes int32 hashes and nothing else (the reference hashes on the
+    host with a Python loop over envs every step); the two float64 count tables are brought up to date once per rollout,
+    step by step in the reference's order and bit-identical to its loop - the env groups run a step apart, so they
+    cannot be updated during the rollout - and the count-based bonus is added to `int_rewards` before its clip;
   * data parallelism: env columns are sharded over ranks (one process per GPU); the only exchanges are one
     RCCL all-reduce of the flat gradient per optimiser step and one of the three advantage moments per
     batch, so an N-GPU run equals a 1-GPU run with N*A envs up to minibatch composition.
@@ -106,11 +111,15 @@ class Runner:
         self.rnd = model.rnd if getattr(model, "use_rnd", False) else None
         if bool(args.rnd.enabled) != (self.rnd is not None):
             raise ValueError("--rnd_enabled and TVFModel(use_rnd=...) must agree")
-        if self.VH != (2 if self.rnd is not None else 1):
-            raise NotImplementedError("value heads: ('ext',), or ('ext', 'int') with RND")
+        # intrinsic rewards in use (rl/config.py:881-883): RND's prediction error, the hash bonus, or their sum
+        self.intrinsic = bool(args.use_intrinsic_rewards)
+        if self.VH != (2 if self.intrinsic else 1):
+            raise NotImplementedError("value heads: ('ext',), or ('ext', 'int') with intrinsic rewards (RND, the hash bonus)")
         self.world, self.rank = parallel.world_size(), parallel.rank()
         if self.rnd is not None and self.world > 1:
             raise NotImplementedError("RND under data parallelism is not built (the predictor's gradient is not reduced)")
+        if args.hash.enabled and self.world > 1:
+            raise NotImplementedError("state hashing under data parallelism is not built (per-rank count tables are not reduced)")
         N, A, nA, VH, dev = self.N, self.A, self.n_actions, self.VH, self.device
         gaussian = action_dist == "gaussian"
         obs_dtype = torch.uint8 if model.policy_net.encoder_kind in ("impala", "nature") and args.env.type != "mujoco" else torch.float32
@@ -153,7 +162,7 @@ class Runner:
             self._tvf_value_weights_dev = torch.as_tensor(self.tvf.value_loss_weights(), device=dev)
             self._ext_estimate = torch.zeros((N + 1, A), dtype=torch.float32, device=dev)
         # ---- intrinsic rewards (rl/rollout.py:243-246, 279-280)
-        if self.rnd is not None:
+        if self.intrinsic:
             self.int_rewards = torch.zeros((N, A), dtype=torch.float32, device=dev)
             self.int_advantage = torch.zeros((N, A), dtype=torch.float32, device=dev)
             self._head_value = torch.zeros((N + 1, A), dtype=torch.float32, device=dev)  # one head's column, unit stride
@@ -164,6 +173,22 @@ class Runner:
             self.intrinsic_reward_norm_scale = 1
             self.intrinsic_returns_rms = RunningMeanStd(shape=())
             self.ems_norm = np.zeros([A])
+        # ---- state hashing (rl/rollout.py:253-274): the hashes of a rollout and the two count tables, all in HBM
+        self.hash = None
+        if args.hash.enabled:
+            from .hashing import LinearStateHasher, StateHashTracker
+            if obs_dtype != torch.uint8 or len(self.state_shape) != 3:
+                raise ValueError("hashing currently requires 8-bit [C, H, W] observations")  # :662
+            normed = args.hash.input in ("normed", "normed_offset")
+            if normed and model.obs_norm is None:
+                raise ValueError(f"--hash_input={args.hash.input} needs --observation_normalization")
+            # the first plane of a frame stack for atari, every element otherwise (:264-268)
+            hash_state_shape = (1, *self.state_shape[1:]) if args.env.type == "atari" else self.state_shape
+            hasher = LinearStateHasher(hash_state_shape, args.hash.bits, device=dev, bias=args.hash.bias)
+            self.hash = StateHashTracker(hasher, N, A, decay=args.hash.decay, bonus=args.hash.bonus,
+                                         bonus_method=args.hash.bonus_method, quantize=int(args.hash.quantize),
+                                         mode=args.hash.input)
+            self._hash_norm = model.obs_norm if normed else None
         # ---- optimisers (rl/rollout.py:126-141)
         self.policy_optimizer = Optimizer(self.policy_net, args.policy_opt)
         self.value_optimizer = Optimizer(self.value_net, args.value_opt) if self.dual else self.policy_optimizer
@@ -319,7 +344,7 @@ class Runner:
 
     @property
     def value_heads(self):
-        return ["ext", "int"] if self.rnd is not None else ["ext"]
+        return ["ext", "int"] if self.intrinsic else ["ext"]
 
     @property
     def tvf_horizons(self):
@@ -344,6 +369,8 @@ class Runner:
         if self.tvf is not None:
             self.tvf.episode_length_buffer.clear()
             self.tvf.episode_length_buffer.append(1000)  # rl/rollout.py:553-555
+        if self.hash is not None:
+            self.hash.reset()  # rl/rollout.py:541-543
         self.time[:] = 0
         self.episode_score[:] = 0
         self.episode_len[:] = 0
@@ -406,6 +433,26 @@ class Runner:
             # rl/rollout.py:764-766 without the host read: one channel-normalise launch, the two networks, and the error
             # straight into this group's columns of row t (the final state's error is never used, :871-878)
             self.rnd.prediction_error(self.all_obs[t, lo:hi], err=self.int_rewards[t, lo:hi], err_stride=1, tag="r" + tag)
+        if self.hash is not None and self._hash_norm is None and t >= 1:
+            # rl/rollout.py:756-757 without the host: row t holds what the envs returned at step t - 1 (the final state
+            # included); one launch on this group's stream writes its hashes, the tables follow after the rollout
+            self.hash.hash_step(self.all_obs[t, lo:hi], t - 1, lo, hi)
+
+    def _hash_normed_row(self, t):
+        """The normed hash inputs read the normaliser's constants as they stand after step t - 1's statistics update and
+        before step t's (rl/rollout.py:735-741, 757): called between the upload of row t and norm.update(all_obs[t])."""
+        if self.hash is not None and self._hash_norm is not None and t >= 1:
+            self.hash.hash_step(self.all_obs[t], t - 1, 0, self.A, norm=self._hash_norm)
+
+    def _finish_hashing(self):
+        """End of a rollout (rl/rollout.py:895-924): bring the tables up to date from obs_hashes, step by step in the
+        reference's order - the env groups run a step apart, so it cannot happen during the rollout - then pay the bonus
+        from the final recent counts, before the clip of the intrinsic rewards (calculate_intrinsic_returns)."""
+        self.hash.update_counts()
+        if self.hash.bonus != 0:
+            self.hash.add_bonus(self.int_rewards)
+        if not args.disable_logging:
+            self.hash.launch_stats()  # read in calculate_returns with the other statistics
 
     def _log_finished(self, finished, ep_len, ep_score, t=None):
         if finished.any():
@@ -428,6 +475,8 @@ class Runner:
         assert self.vec_env is not None, "Please attach vector environment first."
         N, A = self.N, self.A
         self._finished_lengths = [[] for _ in range(N)]
+        if self.intrinsic and self.rnd is None:
+            self.int_rewards.zero_()  # rl/rollout.py:714 (with RND every element is written during the rollout)
         env = self.vec_env
         parts = [env] if self.force_generic_rollout else getattr(env, "parts", [env])
         if not self.force_generic_rollout and all(hasattr(p, "step_arrays") for p in parts):
@@ -452,6 +501,8 @@ class Runner:
                 env.finish_rollout(self._rewards_host.numpy(), self._dones_host.numpy())
         else:
             self._rollout_generic(env)
+        if self.hash is not None:
+            self._finish_hashing()
         self.ext_rewards.copy_(self._rewards_host, non_blocking=True)
         self.terminals.view(torch.uint8).copy_(self._dones_host, non_blocking=True)
         if self.tvf is not None:
@@ -504,7 +555,7 @@ class Runner:
             # the lost steps were real env steps: the vector wrappers' statistics take them in as usual
             env.finish_rollout(self._rewards_host.numpy().copy(), self._dones_host.numpy().copy())
         self._finished_lengths = [[] for _ in range(self.N)]
-        if self.rnd is not None:
+        if self.intrinsic:
             self.int_rewards.zero_()  # rl/rollout.py:714; every element is written again below
         self._rollout_pipelined(parts, [])
 
@@ -615,6 +666,7 @@ class Runner:
                     copy_events[0].record()
                     torch.cuda.set_stream(streams[0])
                     streams[0].wait_event(copy_events[0])
+                    self._hash_normed_row(t)
                     if t < N:
                         norm.update(self.all_obs[t])
                     self._norm_event.record()
@@ -675,6 +727,7 @@ class Runner:
             # zero-copy view: with the process pool self.obs IS the shared pinned block, so this is one async H2D
             src = self.obs if self.obs.flags.c_contiguous else np.ascontiguousarray(self.obs)
             self.all_obs[t].copy_(torch.from_numpy(src), non_blocking=True)
+            self._hash_normed_row(t)
             if norm is not None and t < N:
                 norm.update(self.all_obs[t])
             self._policy_step(t)
@@ -722,12 +775,22 @@ class Runner:
         if self.VH > 1:
             self.ext_returns.copy_(ret_out)
             value = self.ext_value  # (what the log lines below read; _head_value is reused for the int head)
-        if self.rnd is not None:
+        if self.intrinsic:
             self._add_intrinsic_advantage()
         if self.tvf is not None:
             self.tvf.tvf_returns[..., 0].copy_(self.tvf.calculate_tvf_returns(value_head="ext"))
         if not args.disable_logging:
             self.log_returns(value)
+
+    def log_hashing(self, states, recent):
+        """rl/rollout.py:1243-1250: the visited (hashed) states so far, how many this rollout added, and the bins whose
+        recent count is at least 1.  The two counts were reduced on the device at the end of the rollout and came to the
+        host in log_returns' one copy."""
+        states, recent = int(states), int(recent)
+        old = self.log["hash_states"] if "hash_states" in self.log else 0  # the value logged after the previous rollout
+        self.log.watch("hash_states", states, display_width=8, display_name="h_states")
+        self.log.watch("*hash_delta", int(states - old), display_name="h_delta")
+        self.log.watch("*hash_recent", recent, display_name="h_batch")
 
     def calculate_intrinsic_returns(self):
         """rl/rollout.py:1140-1180 (and the clip of :929): normalises `int_rewards` in place and fills `int_advantage`
@@ -803,7 +866,11 @@ class Runner:
         for i, head in enumerate(self.value_heads):
             named.append((f"*return_{head}", self.returns[..., i], {"display_width": 0}))
             named.append((f"value_{head}", self.value[..., i], {"display_name": "v_" + head}))
-        value_quality.log_batch_moments(self.log, named)
+        # (the two hashing counts, int64 on the device, ride along in the same device->host copy)
+        counts = self.hash.device_stats if self.hash is not None else None
+        extra = value_quality.log_batch_moments(self.log, named, extra=counts)
+        if self.hash is not None:
+            self.log_hashing(*extra)
         self.log.watch_mean("reward_scale", self.reward_scale, display_width=0, history_length=1)
         self.log.watch_mean("entropy_bonus", self.current_entropy_bonus, display_width=0, history_length=1)
         self.log.watch("*gamma", args.gamma)
@@ -1266,12 +1333,14 @@ class Runner:
                 data["rnd_optimizer_state_dict"] = self.rnd_optimizer.state_dict()  # rl/rollout.py:416-417
         if self.model.obs_norm is not None:
             data["obs_rms"] = self.model.obs_norm.state_dict()  # rl/rollout.py:438-439
-        if self.rnd is not None:
+        if self.intrinsic:
             # rl/rollout.py:434-436; the reference pickles the RunningMeanStd object, here its three float64 moments
             data["ems_norm"] = self.ems_norm.copy()
             rms = self.intrinsic_returns_rms
             data["intrinsic_returns_rms"] = {"mean": np.float64(rms.mean), "var": np.float64(rms.var),
                                              "count": float(rms.count)}
+        if self.hash is not None:
+            data.update(self.hash.state_dict())  # rl/rollout.py:409-411: hash_global_counts, hash_recent_counts
         return checkpoint.save(data, filename, bool(args.checkpoint_compression))
 
     def load_checkpoint(self, checkpoint_path):
@@ -1288,10 +1357,12 @@ class Runner:
                 opt.load_state_dict(cp[key])
         if self.model.obs_norm is not None:
             self.model.obs_norm.load_state_dict(cp["obs_rms"])  # rl/rollout.py:511-513
-        if self.rnd is not None:  # rl/rollout.py:507-509
+        if self.intrinsic:  # rl/rollout.py:507-509
             self.ems_norm = np.asarray(cp["ems_norm"], np.float64).copy()
             rms = cp["intrinsic_returns_rms"]
             self.intrinsic_returns_rms.restore_state((np.float64(rms["mean"]), np.float64(rms["var"]), rms["count"]))
+        if self.hash is not None:  # rl/rollout.py:500-502
+            self.hash.load_state_dict(cp)
         self.step = cp["step"]
         self.ep_count = cp.get("ep_count", 0)
         self.batch_counter = cp.get("batch_counter", 0)

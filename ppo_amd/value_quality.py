@@ -41,20 +41,23 @@ def _host(t):
     return t.detach().double().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t, dtype=np.float64)
 
 
-def log_batch_moments(log, named):
+def log_batch_moments(log, named, extra=None):
     """watch_mean_std of each (key, tensor, kwargs) with ONE device->host copy for all of them
-    (rl/rollout.py:1199, 1252-1256)."""
+    (rl/rollout.py:1199, 1252-1256).  `extra`: a small device tensor of scalars that rides along in that copy (counters
+    reduced on the device, say); its values come back as a list of floats."""
     named = [(k, t, kw) for k, t, kw in named if t is not None and t.numel()]
-    if not named:
-        return
+    if not named and extra is None:
+        return []
     rows = []
     for _, t, _ in named:
         var, mean = torch.var_mean(t.detach().double().flatten(), unbiased=False)
         rows += [mean, var.sqrt()]
-    got = torch.stack(rows).cpu().numpy()
+    rows = [r.reshape(1) for r in rows] + ([extra.detach().double().flatten()] if extra is not None else [])
+    got = torch.cat(rows).cpu().numpy()
     for i, (key, _, kw) in enumerate(named):
         log.watch(f"{key}_mean", float(got[2 * i]), **kw)
         log.watch(f"{key}_std", float(got[2 * i + 1]), **kw)
+    return [float(v) for v in got[2 * len(named):]]
 
 
 def log_feature_statistics(log, model_out):

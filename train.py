@@ -38,7 +38,7 @@ def make_model(log):
         tvf_feature_sparsity=args.tvf.feature_sparsity, tvf_feature_window=args.tvf.feature_window,
         head_scale=args.model.head_scale,
         head_bias=args.model.head_bias, use_rnd=args.rnd.enabled,
-        value_head_names=("ext", "int") if args.rnd.enabled else ("ext",),
+        value_head_names=("ext", "int") if args.use_intrinsic_rewards else ("ext",),
         observation_normalization=args.observation_normalization,
         freeze_observation_normalization=args.freeze_observation_normalization,
         norm_eps=args.observation_normalization_epsilon,
