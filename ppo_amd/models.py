@@ -11,7 +11,9 @@ and the RCCL gradient all-reduce are single launches) and are exposed under the 
 torch is used for device memory, views and (on the CPU, at construction only) the reference's
 parameter initialisers; no torch operator is on the forward/backward path.
 """
+import contextlib
 import ctypes
+import functools
 import math
 import os
 from collections import OrderedDict
@@ -112,6 +114,31 @@ HEAD_NAMES = ("policy_head", "value_head", "advantage_head", "tvf_head")
 
 def _p(t):
     return None if t is None else t.data_ptr()
+
+
+@functools.lru_cache(maxsize=None)
+def _conv_names(si, reverse=False, firstconv=False, n_block=2):
+    """Parameter names of stack si's block convolutions in forward order (block 0: conv0, conv1; block 1: ...), with
+    `firstconv` behind the stack's first convolution.  `reverse`: the order the backward pass processes them in."""
+    names = [f"encoder.stacks.{si}.blocks.{bi}.conv{ci}" for bi in range(n_block) for ci in range(2)]
+    if firstconv:
+        names.insert(0, f"encoder.stacks.{si}.firstconv")
+    return tuple(reversed(names)) if reverse else tuple(names)
+
+
+def _save_block_maps(acts, si, p, a0, q0, a1):
+    """What the backward pass (and tools/debug_backward.py) reads of a two-block stack: per block its input and the
+    map between its convolutions."""
+    acts[f"q{si}_0_in"], acts[f"a{si}_0"], acts[f"q{si}_1_in"], acts[f"a{si}_1"] = p, a0, q0, a1
+
+
+def _block_wgrad_problems(si, maps, g, grads):
+    """The weight-gradient problems [(input, output gradient, parameter name)] of a two-block stack in processing
+    order: `maps` and `grads` as _block_grads returns them, g the gradient of the stack's output."""
+    p_in, a0, q0, a1 = maps
+    da1, g1, da0, _g0 = grads
+    b1c1, b1c0, b0c1, b0c0 = _conv_names(si, reverse=True)
+    return [(a1, g, b1c1), (q0, da1, b1c0), (a0, g1, b0c1), (p_in, da0, b0c0)]
 
 
 # ----------------------------------------------------------------------------------------------
@@ -430,12 +457,13 @@ class DualHeadNet:
         self._rec = None   # launch recorder (see encode)
         # (n_actions, temperature, seed, offset, log_policy, actions, log_pac, raw_policy, values, n_value_heads) of
         # ppo_dense_heads_act_forward_f32, set by the caller of an inference encode(); None again once a launch took it
+        # (_dense_heads, or encode()'s replay of a recorded launch list)
         self.act_tail = None
-        self._chain_split_usable = None  # decided at the first split launch (see _encode_impala)
+        self._chain_split_usable = None  # decided at the first split launch (see _chain_split_first_use)
         self.allow_chain_split = False   # set by a caller that checks chain_split_error() afterwards
         self.obs_index = None  # [B] int32 (device): the next TRAINING forward reads observation i at x[obs_index[i]] (see takes_obs_index)
         self.loss_tail = None  # arguments of the PPO loss for the next training forward's dense + heads launch (ppo_minibatch)
-        self._tail_ptrs = {}  # stack index -> pointer arrays of the fused residual-block kernel
+        self._tail_ptrs = {}  # pointer arrays of the fused stack kernels, by stack index or (form, stack index): _packed_ptrs
         self.obs_norm = None  # shared ObsNormalizer (set by TVFModel when observation_normalization is on)
         self.grad_ready_hook = None  # callable(stream), see _backward_impala (data-parallel gradient buckets)
         self._split_ws = {}  # workspaces of the two-workgroups-per-image chain launch
@@ -509,15 +537,14 @@ class DualHeadNet:
         nbytes = int(self.lib.ppo_impala_stack_tail_bf16x3_packed_bytes())
         for si, (_cin, cout, _h, _w, ho, wo) in enumerate(self.spec.stacks):
             if not self.lib.ppo_impala_stack_tail_bf16x3_supported(cout, ho, wo) \
-                    or f"encoder.stacks.{si}.blocks.0.conv0" in self._generic:
+                    or _conv_names(si)[0] in self._generic:
                 continue
-            for tr, order in ((0, ((0, 0), (0, 1), (1, 0), (1, 1))), (1, ((1, 1), (1, 0), (0, 1), (0, 0)))):
+            for tr in (0, 1):  # the transposed packing in the backward pass's processing order
                 buf = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
                 self._pk16[(si, tr)] = buf
-                ws = [self.params[f"encoder.stacks.{si}.blocks.{bi}.conv{ci}.weight"].data_ptr() for bi, ci in order]
+                ws = [self.params[n + ".weight"].data_ptr() for n in _conv_names(si, reverse=bool(tr))]
                 jobs.append(_lib.SplitPackJob((ctypes.c_void_p * 4)(*ws), buf.data_ptr(), cout, tr))
-            names = [f"encoder.stacks.{si}.blocks.{bi}.conv{ci}" for bi in range(2) for ci in range(2)]
-            self._pk16[(si, "bias")] = (ctypes.c_void_p * 4)(*[self.params[n + ".bias"].data_ptr() for n in names])
+            self._pk16[(si, "bias")] = (ctypes.c_void_p * 4)(*[self.params[n + ".bias"].data_ptr() for n in _conv_names(si)])
         if jobs:
             self._split_jobs = (_lib.SplitPackJob * len(jobs))(*jobs)
             self.split_bf16 = True
@@ -655,8 +682,7 @@ class DualHeadNet:
                     if not lib.ppo_conv3x3_any_supported(cin, cout, h, w):
                         raise _lib.PpoAmdError(f"no 3x3 convolution kernel for {cin}->{cout} on {h}x{w}")
                 if not specialised((IN_RELU,), cout, cout, ho, wo, True):
-                    self.generic_convs += [f"encoder.stacks.{si}.blocks.{bi}.conv{ci}" for bi in range(sp.n_block)
-                                           for ci in range(2)]
+                    self.generic_convs += _conv_names(si, n_block=sp.n_block)
                     if not lib.ppo_conv3x3_any_supported(cout, cout, ho, wo):
                         raise _lib.PpoAmdError(f"no 3x3 convolution kernel for {cout}->{cout} on {ho}x{wo}")
         self._generic = frozenset(self.generic_convs)
@@ -732,16 +758,13 @@ class DualHeadNet:
     def _refresh_packed(self):
         if self._packed_dirty:
             self._packed_dirty = False
-            rec, self._rec = self._rec, None  # never part of a recorded forward: the refresh is conditional
-            try:
+            with self._unrecorded():  # never part of a recorded forward: the refresh is conditional
                 if self._pack_table is not None:
                     self._call("ppo_conv3x3_pack_weights_f32", ctypes.addressof(self._pack_table), len(self._pack_table))
                 if self.split_bf16:
                     self._call("ppo_impala_stack_tail_pack_bf16x3_jobs", ctypes.addressof(self._split_jobs), len(self._split_jobs))
                     if self._split_conv_jobs is not None:
                         self._call("ppo_conv3x3_pack_bf16x3_jobs", ctypes.addressof(self._split_conv_jobs), len(self._split_conv_jobs))
-            finally:
-                self._rec = rec
 
     def load_state_dict(self, sd, strict=True):
         self.mark_weights_changed()
@@ -774,6 +797,16 @@ class DualHeadNet:
         rc = fn(*args, _lib.current_stream())
         if rc != 0:
             _lib.check(rc, fn_name)
+
+    @contextlib.contextmanager
+    def _unrecorded(self):
+        """Launches made inside are kept out of the launch list that encode() is recording, if it is recording one;
+        yields that list (or None) for the caller to append what a replay should launch instead."""
+        rec, self._rec = self._rec, None
+        try:
+            yield rec
+        finally:
+            self._rec = rec
 
     def _linear(self, x, k, wname, out, relu_x=0, tag=""):
         """out[B, n] = f(x)[B, k] @ W[n, k]^T + b  (torch.nn.Linear).  `tag` keys the split-K workspace, so
@@ -904,34 +937,61 @@ class DualHeadNet:
                        _p(self.params[f"encoder.{name}.bias"]), _p(y), 1, B, cin, h, w, cout, k, k, s)
             acts[name] = y
             cur, mode = y, IN_NONE
-        flat = cur.view(B, sp.flat)  # conv3's output, already through its ReLU
+        # conv3's output is already through its ReLU
+        return self._dense_heads(cur.view(B, sp.flat), 0, "encoder.fc", tag, train, acts)
+
+    def _dense_heads(self, flat, relu_x, wname, tag, train, acts):
+        """The encoder's last linear layer `wname` on relu(flat) (relu_x = 1) or flat (0), and - where the encoder
+        activation is relu - the fused heads behind it in the same launch (the K-slice reduction of the dense product and
+        the heads share it; heads() hands the result out).  That launch also takes the discrete PPO loss on the finished
+        head row (a training forward under `loss_tail`: no loss launch) or the rollout's action step (an inference
+        forward under `act_tail`); either attribute is None again once a launch took it.  Fills acts' 'flat', 'h' and,
+        with the fused launch, 'heads'."""
+        sp, B = self.spec, flat.shape[0]
         h = self._buf(f"{tag}h", (B, sp.hidden_units))
         if self.encoder_activation_fn == "relu":
             o = self._buf(f"{tag}heads", (B, self.nh))
             ws_bytes = self.lib.ppo_gemm_workspace_bytes(B, sp.hidden_units, sp.flat)
             ws = self._ws("gemm_ws" + tag, ws_bytes)
-            args = (_p(flat), 0, _p(self.params["encoder.fc.weight"]), _p(self.params["encoder.fc.bias"]), _p(self.w_heads),
+            args = (_p(flat), relu_x, _p(self.params[wname + ".weight"]), _p(self.params[wname + ".bias"]), _p(self.w_heads),
                     _p(self.b_heads), 1, _p(h), _p(o), B, sp.flat, sp.hidden_units, self.nh, _p(ws), ws_bytes)
             if train and self.loss_tail is not None:
                 tail, self.loss_tail = self.loss_tail, None
                 self._call("ppo_dense_heads_loss_forward_f32", *args, *tail)
             elif self.act_tail is not None and not train:
-                # the recorded launch list keeps the plain form; its replay adds the tail of its own env step (see encode)
+                # the recorded launch list keeps the plain form: its replay adds the tail of its own env step (see encode)
                 tail, self.act_tail = self.act_tail, None
-                rec, self._rec = self._rec, None
-                try:
+                with self._unrecorded() as rec:
                     self._call("ppo_dense_heads_act_forward_f32", *args, *tail)
-                finally:
-                    self._rec = rec
                 if rec is not None:
                     rec.append((self.lib.ppo_dense_heads_forward_f32, "ppo_dense_heads_forward_f32", args))
             else:
                 self._call("ppo_dense_heads_forward_f32", *args)
             acts["heads"] = o
         else:
-            self._linear(flat, sp.flat, "encoder.fc", h, tag=tag)
+            self._linear(flat, sp.flat, wname, h, relu_x=relu_x, tag=tag)
         acts["flat"], acts["h"] = flat, h
         return acts
+
+    def _packed_ptrs(self, key, names, transposed, biases=False, split=None):
+        """The host array of the packed-weight pointers (forward operands, or the transposed ones of backward-data) of
+        the convolutions `names`, cached in _tail_ptrs[key]: packed buffers and parameter views keep their addresses
+        for the life of the net.  `biases`: (that array, the array of their bias pointers); `split`: two arrays, of the
+        first `split` names and of the rest.  None - and nothing cached - while a packed view is missing."""
+        cached = self._tail_ptrs.get(key)
+        if cached is None:
+            pks = [self._pk.get((n, transposed)) for n in names]
+            if any(pk is None for pk in pks):
+                return None
+            ptrs = [pk.data_ptr() for pk in pks]
+            if split:
+                cached = ((ctypes.c_void_p * split)(*ptrs[:split]), (ctypes.c_void_p * (len(ptrs) - split))(*ptrs[split:]))
+            else:
+                cached = (ctypes.c_void_p * len(ptrs))(*ptrs)
+            if biases:
+                cached = (cached, (ctypes.c_void_p * len(names))(*[self.params[n + ".bias"].data_ptr() for n in names]))
+            self._tail_ptrs[key] = cached
+        return cached
 
     def _stack_full_ptrs(self, si, cin, cout, h, w):
         """Host arrays of the five packed-weight / bias pointers (firstconv + the four block convolutions) of stack
@@ -939,35 +999,15 @@ class DualHeadNet:
         if not (FUSE_STACK_FULL and FUSE_STACK_TAIL) or self.spec.n_block != 2 or cin != cout \
                 or not self.lib.ppo_impala_stack_full_supported(cout, h, w) or self.split_bf16:
             return None  # (split mode: the blocks of the 32-channel stacks have their own launches)
-        cached = self._tail_ptrs.get(("full", si))
-        if cached is None:
-            names = [f"encoder.stacks.{si}.firstconv"] + [f"encoder.stacks.{si}.blocks.{bi}.conv{ci}"
-                                                          for bi in range(2) for ci in range(2)]
-            pks = [self._pk.get((n, 0)) for n in names]
-            if any(pk is None for pk in pks):
-                return None
-            cached = ((ctypes.c_void_p * 5)(*[pk.data_ptr() for pk in pks]),
-                      (ctypes.c_void_p * 5)(*[self.params[n + ".bias"].data_ptr() for n in names]))
-            self._tail_ptrs[("full", si)] = cached
-        return cached
+        return self._packed_ptrs(("full", si), _conv_names(si, firstconv=True), 0, biases=True)
 
     def _stack_tail_ptrs(self, si, cout, ho, wo, batch=1 << 30):
         """Host arrays of the four packed-weight / bias pointers of stack si's residual blocks for the fused
-        kernel, or None when it does not apply.  The arrays are cached: packed buffers and parameter views keep
-        their addresses for the life of the net."""
+        kernel, or None when it does not apply."""
         if not FUSE_STACK_TAIL or self.spec.n_block != 2 or not self.lib.ppo_impala_stack_tail_supported(cout, ho, wo) \
                 or (cout == 16 and batch < FUSE_STACK16_MIN_BATCH):
             return None
-        cached = self._tail_ptrs.get(si)
-        if cached is None:
-            names = [f"encoder.stacks.{si}.blocks.{bi}.conv{ci}" for bi in range(2) for ci in range(2)]
-            pks = [self._pk.get((n, 0)) for n in names]
-            if any(pk is None for pk in pks):
-                return None
-            cached = ((ctypes.c_void_p * 4)(*[pk.data_ptr() for pk in pks]),
-                      (ctypes.c_void_p * 4)(*[self.params[n + ".bias"].data_ptr() for n in names]))
-            self._tail_ptrs[si] = cached
-        return cached
+        return self._packed_ptrs(si, _conv_names(si), 0, biases=True)
 
     def _chain_split_ws(self, tag, B, c, h, w):
         """Exchange slots + flags + control words of ppo_impala_stack_chain_split_forward_f32: zeroed ONCE (the flag
@@ -1018,55 +1058,39 @@ class DualHeadNet:
             p = self._buf(f"{tag}p{si}", (B, cout, ho, wo))
             idx = self._buf(f"{tag}idx{si}", (B, cout, ho, wo), torch.uint8) if train else None
             wname = f"encoder.stacks.{si}.firstconv"
+            acts[f"in{si}"], acts[f"idx{si}"] = cur, idx
             full = self._stack_full_ptrs(si, cin, cout, h, w) if cur_mode == IN_NONE else None
             if full is not None:
-                names = [f"{tag}a{si}_0", f"{tag}q{si}_0", f"{tag}a{si}_1", f"{tag}q{si}_1"]
-                a0, q0, a1, q1 = (self._buf(nm, (B, cout, ho, wo)) for nm in names)
+                a0, q0, a1, q1 = self._block_maps(tag, si, B)
                 outs = (_p(p) if train else None, _p(idx), _p(a0) if train else None, _p(q0) if train else None,
                         _p(a1) if train else None, _p(q1), B, cout, h, w)
-                if pending is not None and not train and CHAIN_SPLIT and self.allow_chain_split \
-                        and self._chain_split_usable is not False and B <= CHAIN_SPLIT_MAX_BATCH and (cout, h, w) == (32, 21, 21):
-                    # a rollout group (at most half as many images as CUs): every image on two workgroups that split
-                    # the output channels of the 21x21 convolutions and exchange halves (bit-identical, ~0.7 x the time)
-                    p_prev, ptrs_prev, _saves = pending
-                    pending = None
-                    ws = self._chain_split_ws(tag, B, cout, h, w)
-                    split_args = (_p(p_prev), ptrs_prev[0], ptrs_prev[1], full[0], full[1], _p(q1), _p(ws), ws.numel(),
-                                  B, cout, h, w)
-                    chain_args = (_p(p_prev), ptrs_prev[0], ptrs_prev[1], None, None, None, None, full[0], full[1], *outs)
-                    if self._chain_split_usable is None:
-                        # First use on this device: the exchange goes through the L2 the two workgroups of a pair share,
-                        # which rests on workgroups b and b ^ 8 landing on one XCD.  Both forms once on this batch; if
-                        # the bits differ (another partition mode, another dispatch order) the one-workgroup form stays.
-                        rec, self._rec = self._rec, None
-                        try:
-                            self._call("ppo_impala_stack_chain_split_forward_f32", *split_args)
-                            got = q1.clone()
-                            self._call("ppo_impala_stack_chain_forward_f32", *chain_args)
-                            self._chain_split_usable = bool(torch.equal(got, q1)) and not self.chain_split_error()
-                        finally:
-                            self._rec = rec
-                        if not self._chain_split_usable:
-                            import warnings
-                            warnings.warn("the two-workgroups-per-image chain launch does not reproduce the one-workgroup "
-                                          "launch on this device; using the latter (PPO_AMD_CHAIN_SPLIT=0 silences this)")
-                        if rec is not None:  # the recorded launch list gets the form that was chosen (q1 holds its result)
-                            name = "ppo_impala_stack_chain_split_forward_f32" if self._chain_split_usable \
-                                else "ppo_impala_stack_chain_forward_f32"
-                            rec.append((getattr(self.lib, name), name, split_args if self._chain_split_usable else chain_args))
-                    elif self._chain_split_usable:
-                        self._call("ppo_impala_stack_chain_split_forward_f32", *split_args)
-                elif pending is not None:
+                if pending is None:
+                    launch = ("ppo_impala_stack_full_forward_f32", _p(cur), full[0], full[1], *outs)
+                else:
                     # the previous stack's blocks run inside the same launch, on its pooled map
                     p_prev, ptrs_prev, (pa0, pq0, pa1, pq1) = pending
                     pending = None
-                    self._call("ppo_impala_stack_chain_forward_f32", _p(p_prev), ptrs_prev[0], ptrs_prev[1],
-                               _p(pa0) if train else None, _p(pq0) if train else None, _p(pa1) if train else None,
-                               _p(pq1) if train else None, full[0], full[1], *outs)
-                else:
-                    self._call("ppo_impala_stack_full_forward_f32", _p(cur), full[0], full[1], *outs)
-                acts[f"in{si}"], acts[f"idx{si}"] = cur, idx
-                acts[f"q{si}_0_in"], acts[f"a{si}_0"], acts[f"q{si}_1_in"], acts[f"a{si}_1"] = p, a0, q0, a1
+                    launch = ("ppo_impala_stack_chain_forward_f32", _p(p_prev), ptrs_prev[0], ptrs_prev[1],
+                              _p(pa0) if train else None, _p(pq0) if train else None, _p(pa1) if train else None,
+                              _p(pq1) if train else None, full[0], full[1], *outs)
+                    if not train and CHAIN_SPLIT and self.allow_chain_split and self._chain_split_usable is not False \
+                            and B <= CHAIN_SPLIT_MAX_BATCH and (cout, h, w) == (32, 21, 21):
+                        # a rollout group (at most half as many images as CUs): every image on two workgroups that split
+                        # the output channels of the 21x21 convolutions and exchange halves (bit-identical, ~0.7 x the time)
+                        ws = self._chain_split_ws(tag, B, cout, h, w)
+                        two_wg = ("ppo_impala_stack_chain_split_forward_f32", _p(p_prev), ptrs_prev[0], ptrs_prev[1],
+                                  full[0], full[1], _p(q1), _p(ws), ws.numel(), B, cout, h, w)
+                        if self._chain_split_usable is None:
+                            # the check ran both forms and q1 holds the chosen one's result: a replay launches that one
+                            name, *args = self._chain_split_first_use(two_wg, launch, q1)
+                            if self._rec is not None:
+                                self._rec.append((getattr(self.lib, name), name, tuple(args)))
+                            launch = None
+                        else:
+                            launch = two_wg
+                if launch is not None:
+                    self._call(*launch)
+                _save_block_maps(acts, si, p, a0, q0, a1)
                 cur, cur_mode = q1, IN_NONE
                 continue
             if self.split_bf16 and (wname, 0) in self._pk16 and cur_mode != IN_U8 and cur.dtype == torch.float32:
@@ -1096,12 +1120,14 @@ class DualHeadNet:
                 c = self._buf(f"{tag}c{si}", (B, cout, h, w))
                 self._conv(cur, cur_mode, wname, c, None, B, cin, cout, h, w)
                 self._call("ppo_maxpool3x3s2_forward_f32", _p(c), _p(p), _p(idx), B, cout, h, w)
-            acts[f"in{si}"], acts[f"idx{si}"] = cur, idx
-            q = p
-            if self.split_bf16 and (si, 0) in self._pk16:
+            split = self.split_bf16 and (si, 0) in self._pk16
+            tail = None if split else self._stack_tail_ptrs(si, cout, ho, wo, B)
+            if split or tail is not None:
+                a0, q0, a1, q1 = self._block_maps(tag, si, B)
+                _save_block_maps(acts, si, p, a0, q0, a1)
+                cur, cur_mode = q1, IN_NONE
+            if split:
                 # --precision=low|medium: this stack's residual blocks as the split-bf16 launch
-                names = [f"{tag}a{si}_0", f"{tag}q{si}_0", f"{tag}a{si}_1", f"{tag}q{si}_1"]
-                a0, q0, a1, q1 = (self._buf(nm, (B, cout, ho, wo)) for nm in names)
                 if train and cout == 16:  # (measured: 82 -> 61 us for the 16-channel backward chain; nothing at 32 channels)
                     # the backward chain's gates as sign maps (1 byte per 4 elements instead of 4 float32 maps read for a sign)
                     sg = [self._buf(f"{tag}sg{si}_{k}", (B, cout // 4, ho, wo), torch.uint8) for k in range(4)]
@@ -1112,28 +1138,20 @@ class DualHeadNet:
                     self._call("ppo_impala_stack_tail_forward_bf16x3", _p(p), _p(self._pk16[(si, 0)]), self._pk16[(si, "bias")],
                                _p(a0) if train else None, _p(q0) if train else None, _p(a1) if train else None, _p(q1), B, cout,
                                ho, wo)
-                acts[f"q{si}_0_in"], acts[f"a{si}_0"], acts[f"q{si}_1_in"], acts[f"a{si}_1"] = p, a0, q0, a1
-                cur, cur_mode = q1, IN_NONE
                 continue
-            tail = self._stack_tail_ptrs(si, cout, ho, wo, B)
             if tail is not None:
-                names = [f"{tag}a{si}_0", f"{tag}q{si}_0", f"{tag}a{si}_1", f"{tag}q{si}_1"]
-                a0, q0, a1, q1 = (self._buf(nm, (B, cout, ho, wo)) for nm in names)
                 nxt = sp.stacks[si + 1] if si + 1 < len(sp.stacks) else None
                 if FUSE_STACK_CHAIN and nxt is not None and (nxt[0], nxt[2], nxt[3]) == (cout, ho, wo) \
                         and self._stack_full_ptrs(si + 1, nxt[0], nxt[1], nxt[2], nxt[3]) is not None:
                     # the next stack's launch takes these blocks along (their output stays in LDS on the way)
                     pending = (p, tail, (a0, q0, a1, q1))
-                    acts[f"q{si}_0_in"], acts[f"a{si}_0"], acts[f"q{si}_1_in"], acts[f"a{si}_1"] = p, a0, q0, a1
-                    cur, cur_mode = q1, IN_NONE
                     continue
                 # inference needs only the stack's output; training keeps the maps the backward pass reads
                 # (the 16-channel form re-reads q0 for its second block's skip connection: it is written in inference too)
                 self._call("ppo_impala_stack_tail_forward_f32", _p(p), tail[0], tail[1], _p(a0) if train else None,
                            _p(q0) if (train or cout == 16) else None, _p(a1) if train else None, _p(q1), B, cout, ho, wo)
-                acts[f"q{si}_0_in"], acts[f"a{si}_0"], acts[f"q{si}_1_in"], acts[f"a{si}_1"] = p, a0, q0, a1
-                cur, cur_mode = q1, IN_NONE
                 continue
+            q = p
             for bi in range(sp.n_block):
                 a = self._buf(f"{tag}a{si}_{bi}", (B, cout, ho, wo))
                 qn = self._buf(f"{tag}q{si}_{bi}", (B, cout, ho, wo))
@@ -1151,39 +1169,32 @@ class DualHeadNet:
                 acts[f"q{si}_{bi}_in"], acts[f"a{si}_{bi}"] = q, a
                 q = qn
             cur, cur_mode = q, IN_NONE
-        flat = cur.view(B, sp.flat)
-        h = self._buf(f"{tag}h", (B, sp.hidden_units))
-        if self.encoder_activation_fn == "relu":
-            # dense layer + fused heads in one call (the K-slice reduction of the dense product and the heads share a
-            # launch); heads() hands the result out
-            o = self._buf(f"{tag}heads", (B, self.nh))
-            w = self.params["encoder.dense.weight"]
-            ws_bytes = self.lib.ppo_gemm_workspace_bytes(B, sp.hidden_units, sp.flat)
-            ws = self._ws("gemm_ws" + tag, ws_bytes)
-            args = (_p(flat), 1, _p(w), _p(self.params["encoder.dense.bias"]), _p(self.w_heads), _p(self.b_heads), 1, _p(h),
-                    _p(o), B, sp.flat, sp.hidden_units, self.nh, _p(ws), ws_bytes)
-            if train and self.loss_tail is not None:
-                # with the discrete PPO loss on the finished head row (ppo_minibatch set the tail): no loss launch
-                tail, self.loss_tail = self.loss_tail, None
-                self._call("ppo_dense_heads_loss_forward_f32", *args, *tail)
-            elif self.act_tail is not None and not train:
-                # with the rollout's action step (see encode); the recorded launch list keeps the plain form, whose
-                # replay adds the tail of its own env step
-                tail, self.act_tail = self.act_tail, None
-                rec, self._rec = self._rec, None
-                try:
-                    self._call("ppo_dense_heads_act_forward_f32", *args, *tail)
-                finally:
-                    self._rec = rec
-                if rec is not None:
-                    rec.append((self.lib.ppo_dense_heads_forward_f32, "ppo_dense_heads_forward_f32", args))
-            else:
-                self._call("ppo_dense_heads_forward_f32", *args)
-            acts["heads"] = o
-        else:
-            self._linear(flat, sp.flat, "encoder.dense", h, relu_x=1, tag=tag)
-        acts["flat"], acts["h"] = flat, h
-        return acts
+        return self._dense_heads(cur.view(B, sp.flat), 1, "encoder.dense", tag, train, acts)
+
+    def _block_maps(self, tag, si, B):
+        """The buffers (a0, q0, a1, q1) of stack si's two residual blocks in scratch-buffer set `tag`: per block the map
+        between its convolutions and its output."""
+        _cin, cout, _h, _w, ho, wo = self.spec.stacks[si]
+        shape = (B, cout, ho, wo)
+        return (self._buf(f"{tag}a{si}_0", shape), self._buf(f"{tag}q{si}_0", shape),
+                self._buf(f"{tag}a{si}_1", shape), self._buf(f"{tag}q{si}_1", shape))
+
+    def _chain_split_first_use(self, split, chain, q1):
+        """First split launch on this device.  The exchange goes through the L2 the two workgroups of a pair share, which
+        rests on workgroups b and b ^ 8 landing on one XCD: both forms - (entry point, *arguments) each - run once on this
+        batch, outside any recorded launch list, and if the bits of their output q1 differ (another partition mode,
+        another dispatch order) the one-workgroup form stays for the life of the net.  Returns the chosen form; q1
+        holds its result."""
+        with self._unrecorded():
+            self._call(*split)
+            got = q1.clone()
+            self._call(*chain)
+            self._chain_split_usable = bool(torch.equal(got, q1)) and not self.chain_split_error()
+        if not self._chain_split_usable:
+            import warnings
+            warnings.warn("the two-workgroups-per-image chain launch does not reproduce the one-workgroup "
+                          "launch on this device; using the latter (PPO_AMD_CHAIN_SPLIT=0 silences this)")
+        return split if self._chain_split_usable else chain
 
     def heads(self, acts, tag="i"):
         """[B, nh] = act(h) @ [policy | value | advantage | tvf]^T (+ bias)  (rl/models.py:467-506).
@@ -1416,35 +1427,30 @@ class DualHeadNet:
                          ctypes.addressof(n_slabs))
             slab_launch(args_, n_slabs, [(wname, ws) for (_x, _dy, wname), ws in zip(problems, wss)], c, c)
 
-        chained = None  # (si, g0): stack si's blocks went through the chained launch of stack si + 1
+        chained = None  # (si, maps, grads): stack si's blocks went through the chained launch of stack si + 1
         for si in reversed(range(len(sp.stacks))):
             cin, cout, hh, ww, ho, wo = sp.stacks[si]
+            fc = f"encoder.stacks.{si}.firstconv"
             chain_w = self._stack_chain_bwd_ptrs(si, B) if chained is None else None
             if chain_w is not None:
                 # this stack's backward-data pass and the previous stack's blocks in one launch; the weight-gradient
                 # launches are those of the separate launches, reading the same buffers
-                pi = si - 1
-                names = ("_1_da", "_1_in", "_0_da", "_0_in")
-                da1, g1, da0, g0 = (self._buf(f"g{si}{nm}", (B, cout, ho, wo)) for nm in names)
-                pda1, pg1, pda0, pg0 = (self._buf(f"g{pi}{nm}", (B, cin, hh, ww)) for nm in names)
+                maps, masks, grads = self._block_grads(acts, si, B)
+                pmaps, pmasks, pgrads = self._block_grads(acts, si - 1, B)
+                da1, g1, da0, g0 = grads
+                pda1, pg1, pda0, pg0 = pgrads
                 dc = self._buf(f"g{si}_dc", (B, cout, hh, ww))
-                g_prev = self._buf(f"g{pi}_top", (B, cin, hh, ww))
-                p_in, a0, q0, a1 = acts[f"q{si}_0_in"], acts[f"a{si}_0"], acts[f"q{si}_1_in"], acts[f"a{si}_1"]
-                masks = (ctypes.c_void_p * 4)(a1.data_ptr(), q0.data_ptr(), a0.data_ptr(), p_in.data_ptr())
-                pmasks = (ctypes.c_void_p * 4)(*[acts[k].data_ptr() for k in
-                                                 (f"a{pi}_1", f"q{pi}_1_in", f"a{pi}_0", f"q{pi}_0_in")])
+                g_prev = self._buf(f"g{si - 1}_top", (B, cin, hh, ww))
                 self._call("ppo_impala_stack_chain_backward_f32", _p(g), chain_w[0], masks, _p(acts[f"idx{si}"]), _p(da1),
                            _p(g1), _p(da0), _p(g0), _p(dc), _p(g_prev), chain_w[1], pmasks, _p(pda1), _p(pg1), _p(pda0),
                            _p(pg0), B, cout, hh, ww)
-                b0, b1 = f"encoder.stacks.{si}.blocks.0", f"encoder.stacks.{si}.blocks.1"
-                wgrad_blocks([(a1, g, b1 + ".conv1"), (q0, da1, b1 + ".conv0"), (a0, g1, b0 + ".conv1"),
-                              (p_in, da0, b0 + ".conv0")], B, cout, ho, wo)
-                if WGRAD_RIDE and WGRAD_BATCH_LAUNCH:
-                    carry.append((acts[f"in{si}"], dc, f"encoder.stacks.{si}.firstconv", B, cin, hh, ww))
+                wgrad_blocks(_block_wgrad_problems(si, maps, g, grads), B, cout, ho, wo)
+                if self._first_wgrad_rides(si):
+                    carry.append((acts[f"in{si}"], dc, fc, B, cin, hh, ww))
                 else:
-                    wgrad(acts[f"in{si}"], IN_NONE, dc, f"encoder.stacks.{si}.firstconv", B, cin, cout, hh, ww)
+                    wgrad(acts[f"in{si}"], IN_NONE, dc, fc, B, cin, cout, hh, ww)
                 g = g_prev
-                chained = (pi, pg0)
+                chained = (si - 1, pmaps, pgrads)
                 continue
             # blocks + max-pool backward + transposed first convolution of the stack in one launch, ...
             full_w = self._stack_full_bwd_ptrs(si, cin, cout, hh, ww) if si > 0 else None
@@ -1456,18 +1462,12 @@ class DualHeadNet:
             if chained is not None and chained[0] == si:
                 # the chained launch above ran this stack's blocks: their weight gradients, then the pool and first conv
                 fused, full_w = True, None
-                b0, b1 = f"encoder.stacks.{si}.blocks.0", f"encoder.stacks.{si}.blocks.1"
-                p_in, a0, q0, a1 = acts[f"q{si}_0_in"], acts[f"a{si}_0"], acts[f"q{si}_1_in"], acts[f"a{si}_1"]
-                wgrad_blocks([(a1, g, b1 + ".conv1"), (q0, self._buf(f"g{si}_1_da", (B, cout, ho, wo)), b1 + ".conv0"),
-                              (a0, self._buf(f"g{si}_1_in", (B, cout, ho, wo)), b0 + ".conv1"),
-                              (p_in, self._buf(f"g{si}_0_da", (B, cout, ho, wo)), b0 + ".conv0")], B, cout, ho, wo)
-                g = chained[1]
+                _si, maps, grads = chained
+                wgrad_blocks(_block_wgrad_problems(si, maps, g, grads), B, cout, ho, wo)
+                g = grads[3]
             elif fused:
-                b0, b1 = f"encoder.stacks.{si}.blocks.0", f"encoder.stacks.{si}.blocks.1"
-                p_in, a0, q0, a1 = acts[f"q{si}_0_in"], acts[f"a{si}_0"], acts[f"q{si}_1_in"], acts[f"a{si}_1"]
-                da1, g1, da0, g0 = (self._buf(nm, (B, cout, ho, wo)) for nm in
-                                    (f"g{si}_1_da", f"g{si}_1_in", f"g{si}_0_da", f"g{si}_0_in"))
-                masks = (ctypes.c_void_p * 4)(a1.data_ptr(), q0.data_ptr(), a0.data_ptr(), p_in.data_ptr())
+                maps, masks, grads = self._block_grads(acts, si, B)
+                da1, g1, da0, g0 = grads
                 if full_w is not None:
                     dc = self._buf(f"g{si}_dc", (B, cout, hh, ww))
                     g_prev = self._buf(f"g{si - 1}_top", (B, cin, hh, ww))
@@ -1482,10 +1482,9 @@ class DualHeadNet:
                 else:
                     self._call("ppo_impala_stack_tail_backward_f32", _p(g), tail_w, masks, _p(da1), _p(g1), _p(da0), _p(g0),
                                B, cout, ho, wo)
-                wgrad_blocks([(a1, g, b1 + ".conv1"), (q0, da1, b1 + ".conv0"), (a0, g1, b0 + ".conv1"),
-                              (p_in, da0, b0 + ".conv0")], B, cout, ho, wo)
+                wgrad_blocks(_block_wgrad_problems(si, maps, g, grads), B, cout, ho, wo)
                 if full_w is not None:
-                    wgrad(acts[f"in{si}"], IN_NONE, dc, f"encoder.stacks.{si}.firstconv", B, cin, cout, hh, ww)
+                    wgrad(acts[f"in{si}"], IN_NONE, dc, fc, B, cin, cout, hh, ww)
                     g = g_prev
                     continue
                 g = g0
@@ -1515,23 +1514,19 @@ class DualHeadNet:
             # max-pool backward, then the stack's first convolution
             x_in = acts[f"in{si}"]
             mode = IN_NONE if si > 0 else (IN_U8 if x_in.dtype == torch.uint8 else IN_NONE)
-            if si == 0 and WGRAD_POOLED_DY and f"encoder.stacks.{si}.firstconv" not in self._generic \
+            if si == 0 and WGRAD_POOLED_DY and fc not in self._generic \
                     and lib.ppo_conv3x3_backward_weight_pooled_supported(cin, cout, hh, ww):
                 # nothing else reads this stack's pre-pool gradient: the weight-gradient kernel forms it band by band
-                wgrad(x_in, mode, g, f"encoder.stacks.{si}.firstconv", B, cin, cout, hh, ww, argmax=acts[f"idx{si}"])
+                wgrad(x_in, mode, g, fc, B, cin, cout, hh, ww, argmax=acts[f"idx{si}"])
                 continue
             dc = self._buf(f"g{si}_dc", (B, cout, hh, ww))
             self._call("ppo_maxpool3x3s2_backward_f32", _p(g), _p(acts[f"idx{si}"]), _p(dc), B, cout, hh, ww)
-            if WGRAD_RIDE and WGRAD_BATCH_LAUNCH and si > 0 and cin == cout \
-                    and f"encoder.stacks.{si}.firstconv" not in self._generic \
-                    and mode == IN_NONE and sp.n_block == 2 and sp.stacks[si - 1][1] == cin \
-                    and tuple(sp.stacks[si - 1][4:6]) == (hh, ww):
-                carry.append((x_in, dc, f"encoder.stacks.{si}.firstconv", B, cin, hh, ww))  # rides in the next stack's launch
+            if self._first_wgrad_rides(si):
+                carry.append((x_in, dc, fc, B, cin, hh, ww))
             else:
-                wgrad(x_in, mode, dc, f"encoder.stacks.{si}.firstconv", B, cin, cout, hh, ww)
+                wgrad(x_in, mode, dc, fc, B, cin, cout, hh, ww)
             if si > 0:
                 g = self._buf(f"g{si - 1}_top", (B, cin, hh, ww))
-                fc = f"encoder.stacks.{si}.firstconv"
                 if self.split_bf16 and (fc, 1) in self._pk16:
                     self._call("ppo_conv3x3_bf16x3", _p(dc), 0, _p(self._pk16[(fc, 1)]), None, _p(g), B, cout, cin, hh, ww)
                 else:
@@ -1542,22 +1537,36 @@ class DualHeadNet:
             table = (_lib.WgradJob * len(jobs))(*jobs)
             self._call("ppo_conv3x3_wgrad_reduce_f32", ctypes.addressof(table), len(jobs))
 
+    def _block_grads(self, acts, si, B):
+        """What the backward-data pass of stack si's two residual blocks works on: the saved maps (p_in, a0, q0, a1), the
+        host array of their addresses in processing order (each gradient is gated by the sign of the map its convolution
+        read) and the gradient buffers (da1, g1, da0, g0) - per block, from the last, the gradient of the map between
+        its convolutions and of its input."""
+        _cin, cout, _h, _w, ho, wo = self.spec.stacks[si]
+        shape = (B, cout, ho, wo)
+        p_in, a0, q0, a1 = acts[f"q{si}_0_in"], acts[f"a{si}_0"], acts[f"q{si}_1_in"], acts[f"a{si}_1"]
+        masks = (ctypes.c_void_p * 4)(a1.data_ptr(), q0.data_ptr(), a0.data_ptr(), p_in.data_ptr())
+        return (p_in, a0, q0, a1), masks, (self._buf(f"g{si}_1_da", shape), self._buf(f"g{si}_1_in", shape),
+                                           self._buf(f"g{si}_0_da", shape), self._buf(f"g{si}_0_in", shape))
+
+    def _first_wgrad_rides(self, si) -> bool:
+        """Whether the weight gradient of stack si's first convolution waits for stack si - 1's batched launch, as its
+        fifth problem (WGRAD_RIDE): a c -> c convolution with a specialised kernel, on the geometry of that stack's four
+        block convolutions.  (Its input is read raw: below the first stack no convolution reads uint8.)"""
+        sp = self.spec
+        if not (WGRAD_RIDE and WGRAD_BATCH_LAUNCH) or si < 1 or sp.n_block != 2:
+            return False
+        cin, cout, hh, ww, _ho, _wo = sp.stacks[si]
+        return cin == cout and f"encoder.stacks.{si}.firstconv" not in self._generic \
+            and sp.stacks[si - 1][1] == cin and tuple(sp.stacks[si - 1][4:6]) == (hh, ww)
+
     def _stack_full_bwd_ptrs(self, si, cin, cout, h, w):
         """Host array of the five backward-data packed weights of stack si in processing order (block1.conv1,
         block1.conv0, block0.conv1, block0.conv0, firstconv), or None when the whole-stack kernel does not apply."""
         if not (FUSE_STACK_FULL_BWD and FUSE_STACK_TAIL) or self.spec.n_block != 2 or cin != cout \
                 or not self.lib.ppo_impala_stack_full_supported(cout, h, w):
             return None
-        cached = self._tail_ptrs.get(("full_bwd", si))
-        if cached is None:
-            names = [f"encoder.stacks.{si}.blocks.{bi}.conv{ci}" for bi in (1, 0) for ci in (1, 0)]
-            names.append(f"encoder.stacks.{si}.firstconv")
-            pks = [self._pk.get((n, 1)) for n in names]
-            if any(pk is None for pk in pks):
-                return None
-            cached = (ctypes.c_void_p * 5)(*[pk.data_ptr() for pk in pks])
-            self._tail_ptrs[("full_bwd", si)] = cached
-        return cached
+        return self._packed_ptrs(("full_bwd", si), _conv_names(si, reverse=True, firstconv=True), 1)
 
     def _stack_chain_bwd_ptrs(self, si, batch):
         """(the five backward-data packed weights of stack si, the four of stack si - 1's blocks) as host arrays in
@@ -1571,17 +1580,8 @@ class DualHeadNet:
         if cin != cout or self.spec.stacks[si - 1][1] != cin or tuple(self.spec.stacks[si - 1][4:6]) != (h, w) \
                 or not self.lib.ppo_impala_stack_full_supported(cout, h, w):
             return None
-        cached = self._tail_ptrs.get(("chain_bwd", si))
-        if cached is None:
-            names = [f"encoder.stacks.{s_}.blocks.{bi}.conv{ci}" for s_ in (si, si - 1) for bi in (1, 0) for ci in (1, 0)]
-            names.insert(4, f"encoder.stacks.{si}.firstconv")
-            pks = [self._pk.get((n, 1)) for n in names]
-            if any(pk is None for pk in pks):
-                return None
-            cached = ((ctypes.c_void_p * 5)(*[pk.data_ptr() for pk in pks[:5]]),
-                      (ctypes.c_void_p * 4)(*[pk.data_ptr() for pk in pks[5:]]))
-            self._tail_ptrs[("chain_bwd", si)] = cached
-        return cached
+        names = _conv_names(si, reverse=True, firstconv=True) + _conv_names(si - 1, reverse=True)
+        return self._packed_ptrs(("chain_bwd", si), names, 1, split=5)
 
     def _stack_tail_bwd_ptrs(self, si, cout, ho, wo):
         """Host array of the four backward-data packed weights of stack si's blocks in processing order
@@ -1589,15 +1589,7 @@ class DualHeadNet:
         if not (FUSE_STACK_TAIL and FUSE_STACK_TAIL_BWD >> si & 1) or self.spec.n_block != 2 \
                 or not self.lib.ppo_impala_stack_tail_supported(cout, ho, wo):
             return None
-        cached = self._tail_ptrs.get(("bwd", si))
-        if cached is None:
-            names = [f"encoder.stacks.{si}.blocks.{bi}.conv{ci}" for bi in (1, 0) for ci in (1, 0)]
-            pks = [self._pk.get((n, 1)) for n in names]
-            if any(pk is None for pk in pks):
-                return None
-            cached = (ctypes.c_void_p * 4)(*[pk.data_ptr() for pk in pks])
-            self._tail_ptrs[("bwd", si)] = cached
-        return cached
+        return self._packed_ptrs(("bwd", si), _conv_names(si, reverse=True), 1)
 
     def _bwd_data_fn(self, wname):
         if wname in self._generic:
@@ -1678,8 +1670,8 @@ class DualHeadNet:
         loss_args = (self.n_actions, vh, _p(actions), _p(old_log_pac), _p(old_log_policy), _p(advantages), _p(returns),
                      float(eps_clip), float(ent_coef), float(vf_coef), float(loss_scale) / B,
                      _p(self._buf("dheads", (B, self.nh))), _p(stats), _p(index))
-        # the loss rides on the dense + heads launch of the training forward where that launch exists (IMPALA, relu:
-        # ppo_dense_heads_loss_forward_f32, bit-identical, one latency-bound launch less per minibatch)
+        # the loss rides on the dense + heads launch of the training forward where that launch exists (_dense_heads: image
+        # encoders with relu; ppo_dense_heads_loss_forward_f32, bit-identical, one latency-bound launch less per minibatch)
         self.loss_tail = loss_args
         try:
             acts, o, B, dheads = self._train_forward(prev_state, index, obs_indexed)
@@ -1800,23 +1792,16 @@ class DualHeadNet:
             self._adam_step += 1
             m, v, step = self.exp_avg, self.exp_avg_sq, self._adam_step
         n_part, self._presummed = self._presummed, 0
+        args = (_p(self.flat), _p(self.grad), _p(m), _p(v), self.flat.numel(), step, float(lr), float(beta1), float(beta2),
+                float(eps), float(max_grad_norm), float(grad_div), _p(ws))
         if n_part and scatter is None and grad_div == 1.0:
             # the launch that wrote the gradients left the per-workgroup sums of g^2 in the workspace (fused MLP path)
-            self._call("ppo_adam_step_presummed_f32", _p(self.flat), _p(self.grad), _p(m), _p(v), self.flat.numel(), step,
-                       float(lr), float(beta1), float(beta2), float(eps), float(max_grad_norm), float(grad_div), _p(ws),
-                       n_part, _p(grad_norm_out))
-            self.mask_feature_weights()
-            return
-        if scatter is not None:
+            self._call("ppo_adam_step_presummed_f32", *args, n_part, _p(grad_norm_out))
+        elif scatter is not None:
             # the step also refreshes the convolution kernels' packed operands: no re-pack launch before the next forward
-            self._call("ppo_adam_step_scatter_f32", _p(self.flat), _p(self.grad), _p(m), _p(v), self.flat.numel(), step,
-                       float(lr), float(beta1), float(beta2), float(eps), float(max_grad_norm), float(grad_div), _p(ws),
-                       _p(grad_norm_out), _p(scatter[0]), scatter[1], _p(self._packed))
-            self.mask_feature_weights()
-            return
-        self._call("ppo_adam_step_f32", _p(self.flat), _p(self.grad), _p(m), _p(v), self.flat.numel(), step, float(lr),
-                   float(beta1), float(beta2), float(eps), float(max_grad_norm), float(grad_div), _p(ws),
-                   _p(grad_norm_out))
+            self._call("ppo_adam_step_scatter_f32", *args, _p(grad_norm_out), _p(scatter[0]), scatter[1], _p(self._packed))
+        else:
+            self._call("ppo_adam_step_f32", *args, _p(grad_norm_out))
         self.mask_feature_weights()
 
     # ------------------------------------------------------------------ optimiser state (checkpoints)
