@@ -761,6 +761,36 @@ int ppo_hash_bonus_f32(const int32_t *hashes, int64_t n, const double *recent_co
 int ppo_hash_count_stats(const double *global_counts, const double *recent_counts, int64_t n_bins, int64_t *out, void *stream);
 
 /* ------------------------------------------------------------------------
+ * Experience replay (reference: rl/replay.py `ExperienceReplayBuffer`, host NumPy there).  The buffer is a device array
+ * of rows - opaque bytes: uint8 images and float32 vectors alike - with a companion array of PPO_REPLAY_AUX_FLOATS
+ * float32 per row (the reference's aux record).  One workgroup per row, 16-byte copies where the row length and every
+ * base pointer allow, a byte path otherwise.  No atomics: every launch gives the same bits.  An index outside its
+ * buffer is clamped to the nearest row: nothing is read or written outside a buffer.
+ *
+ * ppo_replay_scatter_rows - rl/replay.py:255-256 and :270-273 (the per-row Python loop of an add):
+ *   for i < n: dst[spot[i]] = src[id[i]], dst_aux[spot[i]] = src_aux[id[i]].  src [n_src_rows, row_bytes],
+ *   dst [n_dst_rows, row_bytes]; src_aux / dst_aux both given or both NULL.  The destinations must be distinct (where
+ *   the reference writes a slot twice the caller keeps the last write); sources may repeat.
+ *
+ * ppo_replay_gather_rows2 - rl/rollout.py:2016-2048 (np.concatenate of buffer and rollout, then the fancy index):
+ *   for i < n: dst[i] = sample[i] < n_a ? a[sample[i]] : b[sample[i] - n_a], likewise the aux records when dst_aux is
+ *   given.  n_b = 0: one source (b, b_aux may be NULL).
+ *
+ * ppo_replay_pairwise_sqdist_u8 - rl/replay.py:99-111 (float32 torch.cdist on the host there):
+ *   out[i * M + j] = sum_k (data[index[i], k] - data[index[j], k])^2 for i, j < M <= PPO_REPLAY_MAX_PAIRWISE_ROWS, as
+ *   int64, exact for every D (partial sums are widened before 32 bits can wrap); data uint8 [n_rows, D].  Symmetric,
+ *   zero diagonal.
+ * ---------------------------------------------------------------------- */
+#define PPO_REPLAY_AUX_FLOATS 16
+#define PPO_REPLAY_MAX_PAIRWISE_ROWS 128
+int ppo_replay_scatter_rows(const void *src, const float *src_aux, int64_t n_src_rows, int64_t row_bytes, const int32_t *id,
+                            const int32_t *spot, int n, void *dst, float *dst_aux, int64_t n_dst_rows, void *stream);
+int ppo_replay_gather_rows2(const void *a, const float *a_aux, int64_t n_a, const void *b, const float *b_aux, int64_t n_b,
+                            int64_t row_bytes, const int32_t *sample, int n, void *dst, float *dst_aux, void *stream);
+int ppo_replay_pairwise_sqdist_u8(const uint8_t *data, int64_t n_rows, int64_t D, const int32_t *index, int M, int64_t *out,
+                                  void *stream);
+
+/* ------------------------------------------------------------------------
  * Synthetic vectorised environment (HOST pointers; runs on host threads).
  * The benchmark workload of SURVEY.md §8(d): obs uint8 i.i.d. uniform, reward ~ N(0,1),
  * done ~ Bernoulli(p_done), auto-reset; stands where the reference has the

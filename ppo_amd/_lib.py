@@ -21,6 +21,7 @@ PPO_IN_NONE, PPO_IN_RELU, PPO_IN_U8 = 0, 1, 2
 PPO_RND_STATS = 5
 PPO_HASH_RAW, PPO_HASH_RAW_CENTERED, PPO_HASH_NORMED, PPO_HASH_NORMED_OFFSET = 0, 1, 2, 3
 PPO_HASH_BONUS_HYPERBOLIC, PPO_HASH_BONUS_QUADRATIC, PPO_HASH_BONUS_BINARY = 0, 1, 2
+PPO_REPLAY_AUX_FLOATS, PPO_REPLAY_MAX_PAIRWISE_ROWS = 16, 128
 
 _vp = ctypes.c_void_p
 _i = ctypes.c_int
@@ -161,6 +162,9 @@ SIGNATURES = {
     "ppo_hash_counts_update_f64": (_i, [_vp, _i, _i, _d, _vp, _vp, _i64, _vp]),
     "ppo_hash_bonus_f32": (_i, [_vp, _i64, _vp, _i64, _i, _d, _d, _vp, _vp]),
     "ppo_hash_count_stats": (_i, [_vp, _vp, _i64, _vp, _vp]),
+    "ppo_replay_scatter_rows": (_i, [_vp, _vp, _i64, _i64, _vp, _vp, _i, _vp, _vp, _i64, _vp]),
+    "ppo_replay_gather_rows2": (_i, [_vp, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _i, _vp, _vp, _vp]),
+    "ppo_replay_pairwise_sqdist_u8": (_i, [_vp, _i64, _i64, _vp, _i, _vp, _vp]),
 }
 
 class PackJob(ctypes.Structure):

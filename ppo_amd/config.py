@@ -3,9 +3,10 @@
 Same flag names, defaults and access pattern as the reference (`rl.config.args`, a global
 singleton read at call time; grouped flags appear as `--<prefix>_<name>` and are read as
 `args.<prefix>.<name>`, rl/config.py:38-185).  Defaults cite rl/config.py line numbers.
-Flags of out-of-scope subsystems (replay, ...) are accepted and ignored with a
+Flags of out-of-scope subsystems are accepted and ignored with a
 note, so existing launch lines keep working.  The `hash` group is registered only on a launch line that enables hashing
-(`--hash_enabled[=True]`): every other line parses exactly as it did before state hashing was built.
+(`--hash_enabled[=True]`), the `replay` group only on one that names a `--replay_mode` other than `off`: every other line
+parses exactly as it did before state hashing and the replay buffer were built.
 """
 import argparse
 import sys
@@ -198,6 +199,35 @@ def hashing_enabled_on(argv):
     return False
 
 
+class ReplayConfig(_Group):  # rl/config.py:357-375
+    MODES = ("off", "overwrite", "sequential", "uniform")
+    FIELDS = (
+        ("mode", str, "off", "[overwrite|sequential|uniform|off]"),
+        ("size", int, 0, "size of the replay buffer (rows, resident in HBM), 0 = off"),
+        ("mixing", bool, False, "distil on a sample of buffer + current rollout"),
+        ("thinning", float, 1.0, "adds this fraction of the experience to the replay buffer"),
+    )
+
+    @property
+    def enabled(self):
+        return self.size > 0 and self.mode != "off"
+
+
+def replay_mode_on(argv):
+    """Whether a launch line names a replay mode other than `off` (`--replay_mode=<m>` or `--replay_mode <m>`): only then
+    are the `replay` flags registered.  On any other line they are unknown flags as before - and in the reference, too,
+    such a line (`--replay_size=5` alone, say) enables nothing."""
+    for i, a in enumerate(argv):
+        value = None
+        if a == "--replay_mode":
+            value = argv[i + 1] if i + 1 < len(argv) else ""
+        elif a.startswith("--replay_mode="):
+            value = a.split("=", 1)[1]
+        if value is not None and value != "off":
+            return True
+    return False
+
+
 class IRConfig(_Group):  # rl/config.py:445-455
     FIELDS = (
         ("propagation", bool, True, "intrinsic returns propagate through the end of an episode"),
@@ -220,6 +250,7 @@ class Config:
         self.rnd = RNDConfig("rnd")
         self.ir = IRConfig("ir")
         self.hash = HashConfig("hash")  # not in _groups: registered per launch line (setup)
+        self.replay = ReplayConfig("replay")  # likewise
         # (a flag belongs to the group with the longest matching prefix: rnd_opt_lr is rnd_opt's, rnd_enabled is rnd's)
         self._groups = (self.policy_opt, self.value_opt, self.distil_opt, self.distil, self.model, self.env, self.tvf,
                         self.rnd_opt, self.rnd, self.ir)
@@ -364,9 +395,11 @@ class Config:
         # the hash flags exist only on a line that enables hashing; on any other line they are unknown flags as before
         # (ignored with a note, in command-line order) and args.hash holds the defaults
         self.hash = HashConfig("hash")
-        groups = self._groups + ((self.hash,) if hashing_enabled_on(argv) else ())
-        if len(groups) > len(self._groups):
-            self.hash.add(parser)
+        self.replay = ReplayConfig("replay")  # the same for the replay flags and a --replay_mode other than off
+        optional = ((self.hash,) if hashing_enabled_on(argv) else ()) + ((self.replay,) if replay_mode_on(argv) else ())
+        groups = self._groups + optional
+        for g in optional:
+            g.add(parser)
         ns, unknown = parser.parse_known_args(argv)
         for k, v in vars(ns).items():
             if any(k.startswith(g._prefix + "_") for g in groups) or k == "use_intrinsic_rewards":
@@ -405,6 +438,13 @@ class Config:
                 raise ValueError(f"Invalid hash_bonus_method {self.hash.bonus_method}")
             if not 1 <= self.hash.bits <= 24:
                 raise ValueError(f"--hash_bits={self.hash.bits}: 1 to 24 bits (two float64 tables of 2^bits entries)")
+        if self.replay.mode not in ReplayConfig.MODES:
+            raise ValueError(f"Invalid replay mode '{self.replay.mode}' (overwrite, sequential, uniform, off)")
+        if self.replay.mode != "off":
+            if self.replay.size <= 0:
+                raise ValueError(f"--replay_mode={self.replay.mode} needs a --replay_size > 0")
+            if not 0 < self.replay.thinning <= 1:
+                raise ValueError(f"--replay_thinning={self.replay.thinning}: a fraction in (0, 1]")
         # EnvConfig.auto (rl/config.py:563-600)
         if self.env.frame_skip in (None, -1):
             self.env.frame_skip = 4 if self.env.type == "atari" else 1
@@ -435,7 +475,7 @@ class Config:
     def flatten(self):
         d = {k: v for k, v in vars(self).items() if not k.startswith("_") and not isinstance(v, _Group)}
         d["use_intrinsic_rewards"] = self.use_intrinsic_rewards
-        for g in self._groups + ((self.hash,) if self.hash.enabled else ()):
+        for g in self._groups + ((self.hash,) if self.hash.enabled else ()) + ((self.replay,) if self.replay.enabled else ()):
             d.update(g.flatten())
         return d
 

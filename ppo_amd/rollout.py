@@ -25,6 +25,10 @@ What changed relative to the reference, and why (MI355X-first):
     host with a Python loop over envs every step); the two float64 count tables are brought up to date once per rollout,
     step by step in the reference's order and bit-identical to its loop - the env groups run a step apart, so they
     cannot be updated during the rollout - and the count-based bonus is added to `int_rewards` before its clip;
+  * experience replay (`--replay_mode`, `--replay_size`, rl/replay.py, rl/rollout.py:956-969, 2016-2138): the buffer lies
+    in HBM next to the rollout; an add is one scatter launch from `all_obs`, the distil batch one gather launch (buffer,
+    or buffer + rollout with `--replay_mixing`) whose targets and old policy are regenerated on the device; which rows
+    go where is the reference's index arithmetic on its np.random draws (ppo_amd/replay.py `plan_add`);
   * data parallelism: env columns are sharded over ranks (one process per GPU); the only exchanges are one
     RCCL all-reduce of the flat gradient per optimiser step and one of the three advantage moments per
     batch, so an N-GPU run equals a 1-GPU run with N*A envs up to minibatch composition.
@@ -120,6 +124,9 @@ class Runner:
             raise NotImplementedError("RND under data parallelism is not built (the predictor's gradient is not reduced)")
         if args.hash.enabled and self.world > 1:
             raise NotImplementedError("state hashing under data parallelism is not built (per-rank count tables are not reduced)")
+        if args.replay.enabled and self.world > 1:
+            raise NotImplementedError("experience replay under data parallelism is not built (every rank would keep a buffer "
+                                      "of its own env columns and draw its own distil batch)")
         N, A, nA, VH, dev = self.N, self.A, self.n_actions, self.VH, self.device
         gaussian = action_dist == "gaussian"
         obs_dtype = torch.uint8 if model.policy_net.encoder_kind in ("impala", "nature") and args.env.type != "mujoco" else torch.float32
@@ -189,6 +196,14 @@ class Runner:
                                          bonus_method=args.hash.bonus_method, quantize=int(args.hash.quantize),
                                          mode=args.hash.input)
             self._hash_norm = model.obs_norm if normed else None
+        # ---- experience replay (rl/rollout.py:295-309): the buffer and a rollout's aux records, in HBM
+        self.replay_buffer = None
+        if args.replay.enabled:
+            from .replay import ExperienceReplayBuffer
+            self.replay_buffer = ExperienceReplayBuffer(max_size=args.replay.size, obs_shape=self.state_shape,
+                                                        obs_dtype=obs_dtype, mode=args.replay.mode,
+                                                        thinning=args.replay.thinning, device=dev)
+            self._replay_aux = torch.zeros((N * A, ExperienceReplayBuffer.N_AUX), dtype=torch.float32, device=dev)
         # ---- optimisers (rl/rollout.py:126-141)
         self.policy_optimizer = Optimizer(self.policy_net, args.policy_opt)
         self.value_optimizer = Optimizer(self.value_net, args.value_opt) if self.dual else self.policy_optimizer
@@ -758,6 +773,10 @@ class Runner:
         """Advantages (lambda_policy) and value targets (lambda_value) in one fused scan
         (rl/rollout.py:1182-1285 -> rl/returns.py:7-67), then the TVF return targets (rl/tvf.py:210-271)."""
         N, A = self.N, self.A
+        if self.replay_buffer is not None:
+            # first, so that the draws of the add come before those of the TVF return sampler below and of the log lines
+            # at the end, as in the reference (whose add closes generate_rollout, rl/rollout.py:956-969)
+            self._add_rollout_to_replay()
         if self.tvf is not None:
             self._ext_estimate.copy_(self.tvf.get_tvf_ext_value_estimate(new_gamma=args.gamma))
             value = self._ext_estimate
@@ -781,6 +800,29 @@ class Runner:
             self.tvf.tvf_returns[..., 0].copy_(self.tvf.calculate_tvf_returns(value_head="ext"))
         if not args.disable_logging:
             self.log_returns(value)
+
+    def _rollout_aux(self, out, time_and_step):
+        """The rollout's aux records [N * A, 16] float32 into `out` (device): reward and action (generate_aux_buffer,
+        rl/rollout.py:2006-2014), with `time_and_step` also the env time and the global step of every row (:957-968; the
+        rollout's steps start where `self.step` stood before it).  vtarg stays 0: the aux phase is not built."""
+        R = type(self.replay_buffer)
+        n = self.N * self.A
+        out.zero_()
+        out[:, R.AUX_REWARD].copy_(self.ext_rewards.view(n))
+        actions = self.actions[:, :, 0] if self.actions.dim() == 3 else self.actions  # continuous: the first one (rl/replay.py:184-186)
+        out[:, R.AUX_ACTION].copy_(actions.reshape(n))
+        if time_and_step:
+            out[:, R.AUX_TIME].copy_(torch.from_numpy(self.all_time[:self.N].reshape(n)).to(self.device, non_blocking=True))
+            start = self.step - n * self.world
+            out[:, R.AUX_STEP].copy_(torch.arange(start, start + n, dtype=torch.int64, device=self.device))
+        return out
+
+    def _add_rollout_to_replay(self):
+        """rl/rollout.py:956-969: the rollout's observations and aux records go into the buffer, read where they lie -
+        one scatter launch (ExperienceReplayBuffer.add_experience)."""
+        n = self.N * self.A
+        self.replay_buffer.add_experience(self.all_obs[:self.N].view(n, *self.state_shape),
+                                          self._rollout_aux(self._replay_aux, time_and_step=True))
 
     def log_hashing(self, states, recent):
         """rl/rollout.py:1243-1250: the visited (hashed) states so far, how many this rollout added, and the bins whose
@@ -877,6 +919,8 @@ class Runner:
         if self.tvf is not None:
             self.log.watch("*tvf_gamma", args.tvf.gamma)
             self.log.watch_stats("*tvf_return_ext", self.tvf.tvf_returns[:, :, -1].cpu().numpy())
+        if self.replay_buffer is not None and self.batch_counter % 4 == 0:
+            self.replay_buffer.log_stats(self.log)  # rl/rollout.py:1272-1276
         if args.disable_ev or self.batch_counter % 4 != 3:
             return
         value_quality.log_feature_statistics(
@@ -951,28 +995,37 @@ class Runner:
             """Also the exit path of a failed step: the parked hook must come back whatever happened."""
             self.net.grad_ready_hook = self.hook
 
-    def _run_epochs(self, label, optimizer, epochs, mini_batch_size, step_fn, n_stats, rows=None):
+    def _run_epochs(self, label, optimizer, epochs, mini_batch_size, step_fn, n_stats, rows=None, obs=None):
         """Permutation minibatching over the rollout (rl/rollout.py:2257-2407): per epoch one host shuffle
         (np.random, as the reference :2319-2320); per minibatch — in micro-batches of at most --max_micro_batch_size
         samples, gradients accumulated, each pass scaled by 1 / micro_batches (:2331-2374) — gather the observations,
         run step_fn(mb_obs, index, loss_scale) -> per-sample stats [n, n_stats], then step the optimiser; the stats
         are column-summed into one device row per minibatch.  `rows`: train on the first `rows` samples of the
-        time-major batch only (the RND phase, rl/rollout.py:1830)."""
-        B = self.N * self.A if rows is None else int(rows)
+        time-major batch only (the RND phase, rl/rollout.py:1830).  `obs`: a contiguous device tensor [S, *state_shape]
+        of the rollout's dtype to train over instead of the rollout's observations (the distil batch drawn from the replay
+        buffer); the per-sample data step_fn reads through the index then has S rows too."""
+        if obs is None:
+            B = self.N * self.A if rows is None else int(rows)
+            obs_all = self.all_obs[:self.N].view(self.N * self.A, *self.state_shape)[:B]
+        else:
+            if rows is not None or obs.dtype != self.all_obs.dtype or tuple(obs.shape[1:]) != self.state_shape \
+                    or not obs.is_contiguous():
+                raise ValueError(f"obs must be a contiguous {self.all_obs.dtype} [S, {self.state_shape}] tensor (and rows unset)")
+            B = int(obs.shape[0])
+            obs_all = obs
         net = optimizer.net
         mb = parallel.local_minibatch(mini_batch_size)  # the flag is the GLOBAL minibatch (SURVEY.md §8e)
         if B % mb:
             raise ValueError(f"batch {B} is not a multiple of the per-rank minibatch {mb}")
         n_mb = B // mb
         micro, n_micro = self._micro_batches(mb)
-        obs_rows = self.all_obs[:self.N].view(self.N * self.A, -1)[:B]
+        obs_rows = obs_all.view(B, -1)
         row_bytes = obs_rows.shape[1] * obs_rows.element_size()
         # MLP nets on the fused path read their rows of the whole batch through the permutation and column-sum the
         # statistics in their weight-gradient launch: no gather launch, no column-sum launch
         fused = bool(getattr(net, "mlp_fused", False)) and net.obs_norm is None and self.all_obs.dtype == torch.float32
         # ... and the IMPALA nets read uint8 image rows through the permutation in their first convolution
         in_conv = not fused and hasattr(net, "takes_obs_index") and net.takes_obs_index(self.all_obs)
-        obs_all = self.all_obs[:self.N].view(self.N * self.A, *self.state_shape)[:B]
         mb_obs = None if (fused or in_conv) else net._buf("mb_obs", (micro, *self.state_shape), self.all_obs.dtype)
         stat_rows = net._buf(f"stat_rows_{label}", (epochs * n_mb, n_stats))
         norm_rows = net._buf(f"norm_rows_{label}", (epochs * n_mb,))
@@ -1065,8 +1118,12 @@ class Runner:
         policy (`before_policy`) or the just-updated policy re-evaluated over the batch (`after_policy`)."""
         N, A = self.N, self.A
         B = N * A
+        if self.replay_buffer is not None:
+            wanted = samples_wanted if samples_wanted is not None else (args.distil.batch_size if args.distil.batch_size > 0 else B)
+            return self._get_replay_distil_batch(int(wanted))
         if samples_wanted not in (None, B) or (0 < args.distil.batch_size != B):
-            raise NotImplementedError("distillation from a replay buffer is out of scope; distil_batch_size = rollout")
+            raise NotImplementedError("without a replay buffer (--replay_mode, --replay_size) distillation trains on the "
+                                      "rollout: distil_batch_size = rollout")
         if args.distil.target != "value" or args.distil.loss != "kl_policy" or args.distil.value_loss != "mse":
             raise NotImplementedError("distil target 'value', loss 'kl_policy', value_loss 'mse' are built")
         use_tvf = self.tvf is not None and not args.distil.force_ext
@@ -1091,6 +1148,52 @@ class Runner:
         batch["old_policy"] = old
         return batch
 
+    def get_replay_sample(self, samples_wanted: int, with_aux=False):
+        """rl/rollout.py:2016-2048 on the device: `samples_wanted` rows of the replay buffer - of buffer + current rollout
+        with --replay_mixing, of the rollout alone while the buffer is empty - drawn as the reference draws them
+        (np.random.choice without replacement, only when fewer rows are wanted than there are), gathered by ONE launch
+        into a [S, *state_shape] device buffer.  Returns (obs, aux or None)."""
+        buf, net = self.replay_buffer, self.policy_net
+        n = self.N * self.A
+        n_a = buf.current_size
+        mix = bool(args.replay.mixing) or n_a == 0
+        total = n_a + (n if mix else 0)
+        if samples_wanted < total:
+            sample = np.random.choice(total, samples_wanted, replace=False)
+        else:
+            sample = np.arange(total)
+        S = len(sample)
+        sample_dev = torch.from_numpy(sample.astype(np.int32)).to(self.device, non_blocking=True)
+        obs = net._buf("replay_sample_obs", (S, *self.state_shape), self.all_obs.dtype)
+        aux = net._buf("replay_sample_aux", (S, buf.N_AUX)) if with_aux else None
+        extra = self.all_obs[:self.N].view(n, *self.state_shape) if mix else None
+        extra_aux = self._rollout_aux(net._buf("replay_mix_aux", (n, buf.N_AUX)), time_and_step=False) if mix and with_aux else None
+        buf.gather(sample_dev, obs, out_aux=aux, extra=extra, extra_aux=extra_aux)
+        return obs, aux
+
+    def _get_replay_distil_batch(self, samples_wanted: int):
+        """The reference's slow path (rl/rollout.py:2114-2138): a sample of the replay buffer, its targets regenerated
+        from value_net and the policy to stay close to from policy_net as they stand now, in chunks of
+        --max_micro_batch_size.  Everything stays on the device."""
+        assert args.distil.target == "value", "Replay distil required value targets."
+        if args.distil.loss != "kl_policy" or args.distil.value_loss != "mse":
+            raise NotImplementedError("distil loss 'kl_policy', value_loss 'mse' are built")
+        use_tvf = self.tvf is not None and not args.distil.force_ext
+        if use_tvf and 0 < args.distil.max_heads < self.K:
+            raise NotImplementedError("distil_max_heads sub-sampling is not built (default: all heads)")
+        obs, _aux = self.get_replay_sample(samples_wanted)
+        S = int(obs.shape[0])
+        pol, val = self.policy_net, self.value_net
+        key = "raw_policy" if self.action_dist == "gaussian" else "log_policy"
+        old = pol._buf("replay_distil_old_policy", (S, self.n_actions))
+        targets = pol._buf("replay_distil_targets", (S, self.K) if use_tvf else (S,))
+        chunk = max(args.max_micro_batch_size, 1)
+        for i in range(0, S, chunk):
+            out = val.forward(obs[i:i + chunk], exclude_policy=True)
+            targets[i:i + chunk].copy_(out["tvf_value"][:, :, 0] if use_tvf else out["value"][:, 0])
+            old[i:i + chunk].copy_(pol.forward(obs[i:i + chunk], exclude_value=True)[key])
+        return {"use_tvf": use_tvf, "prev_state": obs, "distil_targets": targets, "old_policy": old}
+
     def train_distil(self):
         """Distillation phase (rl/rollout.py:2140-2164): policy_net's value (or TVF) heads learn value_net's
         estimates under a KL constraint that keeps the policy where it is."""
@@ -1107,8 +1210,9 @@ class Runner:
                                         use_tvf=batch["use_tvf"], weights=weights, gaussian=gaussian,
                                         loss_scale=loss_scale, index=idx, **kw)
         opt = self.policy_optimizer if args.distil.use_policy_opt else self.distil_optimizer
+        # (with a replay buffer the batch is the sample drawn from it, otherwise the rollout where it lies)
         self._run_epochs("distil", Optimizer(net, args.distil_opt, opt.state), args.distil_opt.epochs,
-                         args.distil_opt.mini_batch_size, step, 4)
+                         args.distil_opt.mini_batch_size, step, 4, obs=batch.get("prev_state"))
 
     def train_rnd(self):
         """The predictor's phase (rl/rollout.py:1824-1841): --rnd_opt_epochs epochs of minibatches over the first
@@ -1341,6 +1445,8 @@ class Runner:
                                              "count": float(rms.count)}
         if self.hash is not None:
             data.update(self.hash.state_dict())  # rl/rollout.py:409-411: hash_global_counts, hash_recent_counts
+        if self.replay_buffer is not None and not disable_replay:
+            data["replay_buffer"] = self.replay_buffer.save_state(force_copy=False)  # rl/rollout.py:431-432
         return checkpoint.save(data, filename, bool(args.checkpoint_compression))
 
     def load_checkpoint(self, checkpoint_path):
@@ -1363,6 +1469,11 @@ class Runner:
             self.intrinsic_returns_rms.restore_state((np.float64(rms["mean"]), np.float64(rms["var"]), rms["count"]))
         if self.hash is not None:  # rl/rollout.py:500-502
             self.hash.load_state_dict(cp)
+        if self.replay_buffer is not None:  # rl/rollout.py:504-505
+            if "replay_buffer" in cp:
+                self.replay_buffer.load_state(cp["replay_buffer"])
+            else:
+                self.log.warn("the checkpoint holds no replay buffer (written with disable_replay): the buffer starts empty")
         self.step = cp["step"]
         self.ep_count = cp.get("ep_count", 0)
         self.batch_counter = cp.get("batch_counter", 0)
