@@ -23,6 +23,32 @@ inline int check_launch(const char *what)
     return PPO_OK;
 }
 
+// Prepare kernel Kern for launches with lds_bytes of dynamic LDS: raise its dynamic-LDS limit and, where the caller passes
+// `occupancy`, ask the runtime how many workgroups of `threads` threads and lds_bytes of LDS are resident per CU.  The
+// HIP calls are made once per kernel instantiation per process; later calls hand back the stored number.  A failure is
+// reported as "<prefix>: ..." and leaves the kernel unprepared, so the next call tries again.  *occupancy is the raw
+// answer of the runtime: clamping it is the launcher's decision.
+// The state is one static per instantiation, neither per device nor locked: a process drives one GPU.  A process with
+// several devices, or launches of one kernel from several threads, would change that here and nowhere else.
+template <auto Kern>
+int prepare_kernel(const char *prefix, size_t lds_bytes, int threads = 0, int *occupancy = nullptr)
+{
+    static int prepared = -1;  // -1 until prepared, then the occupancy (0 where none was asked for)
+    if (prepared < 0) {
+        const void *kern = reinterpret_cast<const void *>(Kern);
+        hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+        if (e != hipSuccess) return fail(PPO_E_HIP, "%s: hipFuncSetAttribute: %s", prefix, hipGetErrorString(e));
+        int nb = 0;
+        if (occupancy) {
+            e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, threads, lds_bytes);
+            if (e != hipSuccess) return fail(PPO_E_HIP, "%s: occupancy query: %s", prefix, hipGetErrorString(e));
+        }
+        prepared = nb < 0 ? 0 : nb;
+    }
+    if (occupancy) *occupancy = prepared;
+    return PPO_OK;
+}
+
 inline bool aligned(const void *p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
 
 // Range-checked reads through a buffer descriptor.  Why they exist: a predicated global load - `ok ? p[i] : 0`,

@@ -63,16 +63,26 @@ __device__ unsigned long long ppo_tune_stamps[8 * 8 * 1024];  // [workgroup][wav
 #define PPO_STAMP_ADD(slot, t1, t0)
 #endif
 
-// Set by the *_packed_f32 entry points around their dispatch: `weight` is then the pre-packed A operand
-// (ppo_conv3x3_pack_weights_f32) instead of the raw [O][I][3][3] tensor.  Host-side, thread-local, consumed by the
-// launch a few frames down the same call.
-thread_local int t_weights_packed = 0;
-// images of the next conv3x3_pool launch are read through this index (ppo_conv3x3_pool_forward_packed_indexed_f32): the
-// minibatch gather of the observations happens in the first convolution's own loads
-thread_local const int32_t *t_in_index = nullptr;
-// the dispatchers below answer "is there a kernel" instead of launching it (the ppo_conv3x3_*_supported probes): one case
-// list serves both, so a probe cannot drift from what a launch accepts
-thread_local int t_probe = 0;
+// One call of a dispatcher, handed from the entry point through dispatch_* to launch_*: everything the result depends on
+// besides the geometry is in here.
+struct ConvArgs {
+    // answer "is there a kernel" (PPO_OK / PPO_E_INVALID) instead of launching it (the ppo_conv3x3_*_supported probes, which
+    // fill in nothing else): one case list serves both, so a probe cannot drift from what a launch accepts
+    bool probe = false;
+    const void *in = nullptr;
+    const float *w = nullptr;
+    // `w` is the pre-packed A operand (ppo_conv3x3_pack_weights_f32) instead of the raw [O][I][3][3] tensor
+    bool packed = false;
+    const float *bias = nullptr;
+    const float *residual = nullptr, *mask_src = nullptr;  // conv3x3 only
+    float *out = nullptr;
+    uint8_t *argmax = nullptr;  // conv3x3_pool only
+    // conv3x3_pool on uint8 observations only, nullable: image i is image in_index[i] of `in` - the minibatch gather of the
+    // observations happens in the first convolution's own loads
+    const int32_t *in_index = nullptr;
+    int n = 0;
+    hipStream_t st = nullptr;
+};
 
 // Packed A operand of a kernel with (kernel-side) CIN input and COUT output channels: for K step s = tap*CINP/4 + cs
 // and channel tile n, lane (l15, g) holds w(co = n*16 + l15, ci = cs*4 + g, tap); four consecutive steps form one
@@ -531,83 +541,67 @@ __global__ __launch_bounds__(NW * 64) void conv3x3_kernel(
 }
 
 template <int CIN, int COUT, int H, int W, int TR, int MT, int NW, int IN_MODE, bool TRANSPOSED, bool PACKED, bool WIDE>
-int launch_conv_impl(const void *in, const float *w, const float *bias, const float *residual,
-                     const float *mask_src, float *out, int n_images, hipStream_t st)
+int launch_conv_impl(const ConvArgs &a)
 {
     using C = ConvCfg<CIN, COUT, H, W, TR, IN_MODE != IN_U8>;
-    auto kern = conv3x3_kernel<CIN, COUT, H, W, TR, MT, NW, IN_MODE, TRANSPOSED, PACKED, WIDE>;
+    constexpr auto kern = conv3x3_kernel<CIN, COUT, H, W, TR, MT, NW, IN_MODE, TRANSPOSED, PACKED, WIDE>;
     constexpr int kConvThreads = NW * 64;
     // the band buffers (+ the WIDE epilogue's per-wave scratch), or the padded weight image the prologue stages
     // through the same region
     constexpr size_t kWeightImage = (size_t)(TRANSPOSED ? CIN : COUT) * (((TRANSPOSED ? COUT : CIN) * 9) | 1) * 4;
     constexpr size_t kBands = C::LDS_BYTES + (WIDE ? (size_t)NW * conv_scratch_floats<MT, C::NT>() * 4 : 0);
     constexpr size_t kLdsBytes = kBands > kWeightImage ? kBands : kWeightImage;
-    static int wg_per_cu = 0;  // resident workgroups per CU (LDS- and VGPR-limited), queried once
-    if (wg_per_cu == 0) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes);
-        if (e != hipSuccess) return fail(PPO_E_HIP, "conv3x3: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        int nb = 0;
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, kConvThreads, kLdsBytes);
-        if (e != hipSuccess) return fail(PPO_E_HIP, "conv3x3: occupancy query: %s", hipGetErrorString(e));
-        wg_per_cu = nb < 1 ? 1 : (nb > 24 / NW ? 24 / NW : nb);
+    int nb = 0;  // resident workgroups per CU (LDS- and VGPR-limited)
+    if (int rc = prepare_kernel<kern>("conv3x3", kLdsBytes, kConvThreads, &nb)) return rc;
+    int wg_per_cu = nb < 1 ? 1 : (nb > 24 / NW ? 24 / NW : nb);
 #ifdef PPO_TUNE_WG_PER_CU  // tools/conv_tune experiment build only
-        wg_per_cu = PPO_TUNE_WG_PER_CU < wg_per_cu ? PPO_TUNE_WG_PER_CU : wg_per_cu;
+    wg_per_cu = PPO_TUNE_WG_PER_CU < wg_per_cu ? PPO_TUNE_WG_PER_CU : wg_per_cu;
 #endif
-    }
-    const int n_items = n_images * C::NBANDS;
+    const int n_items = a.n * C::NBANDS;
     int grid = 256 * wg_per_cu;
     if (grid > n_items) grid = n_items;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kConvThreads), kLdsBytes, st, in, w, bias, residual, mask_src, out,
-                       n_images);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(kConvThreads), kLdsBytes, a.st, a.in, a.w, a.bias, a.residual, a.mask_src,
+                       a.out, a.n);
     return check_launch("conv3x3_kernel");
 }
 
 // raw-weight and packed-weight forms are separate instantiations (a runtime branch between the two prologues cost
 // the backward-data kernels 8 %: 1.56 -> 1.70 ms per minibatch)
 template <int CIN, int COUT, int H, int W, int TR, int MT, int NW, int IN_MODE, bool TRANSPOSED>
-int launch_conv(const void *in, const float *w, const float *bias, const float *residual, const float *mask_src,
-                float *out, int n_images, hipStream_t st)
+int launch_conv(const ConvArgs &a)
 {
     // the 16-byte epilogue needs whole float4s: channel planes and bands a multiple of 4 floats, 16-byte aligned tensors
     constexpr bool kWideGeo = (H * W) % 4 == 0 && (TR * W) % 4 == 0 && IN_MODE != IN_U8;
 #ifdef PPO_TUNE_NO_WIDE
     const bool wide = false;
 #else
-    const bool wide = kWideGeo && aligned(out, 16) && (!residual || aligned(residual, 16)) && (!mask_src || aligned(mask_src, 16));
+    const bool wide = kWideGeo && aligned(a.out, 16) && (!a.residual || aligned(a.residual, 16)) &&
+                      (!a.mask_src || aligned(a.mask_src, 16));
 #endif
     if constexpr (kWideGeo) {
         if (wide) {
-            if (t_weights_packed)
-                return launch_conv_impl<CIN, COUT, H, W, TR, MT, NW, IN_MODE, TRANSPOSED, true, true>(in, w, bias, residual,
-                                                                                                     mask_src, out, n_images, st);
-            return launch_conv_impl<CIN, COUT, H, W, TR, MT, NW, IN_MODE, TRANSPOSED, false, true>(in, w, bias, residual,
-                                                                                                  mask_src, out, n_images, st);
+            if (a.packed) return launch_conv_impl<CIN, COUT, H, W, TR, MT, NW, IN_MODE, TRANSPOSED, true, true>(a);
+            return launch_conv_impl<CIN, COUT, H, W, TR, MT, NW, IN_MODE, TRANSPOSED, false, true>(a);
         }
     }
-    if (t_weights_packed)
-        return launch_conv_impl<CIN, COUT, H, W, TR, MT, NW, IN_MODE, TRANSPOSED, true, false>(in, w, bias, residual, mask_src,
-                                                                                                out, n_images, st);
-    return launch_conv_impl<CIN, COUT, H, W, TR, MT, NW, IN_MODE, TRANSPOSED, false, false>(in, w, bias, residual, mask_src,
-                                                                                             out, n_images, st);
+    if (a.packed) return launch_conv_impl<CIN, COUT, H, W, TR, MT, NW, IN_MODE, TRANSPOSED, true, false>(a);
+    return launch_conv_impl<CIN, COUT, H, W, TR, MT, NW, IN_MODE, TRANSPOSED, false, false>(a);
 }
 
 // Supported layer geometries: Atari 84x84 (rl/atari.py) and Procgen 64x64 (rl/procgen.py)
 // through the three IMPALA stacks (16, 32, 32 channels; rl/models.py:873).
 // TR / MT are chosen so that the pixel-tile groups of a band divide evenly over the 8 waves.
 template <int IN_MODE, bool TRANSPOSED>
-int dispatch_conv(int cin, int cout, int h, int w_, const void *in, const float *w, const float *bias,
-                  const float *residual, const float *mask_src, float *out, int n, hipStream_t st)
+int dispatch_conv(int cin, int cout, int h, int w_, const ConvArgs &a)
 {
 // FIRST: the obs conv (uint8 or float obs, never ReLU-on-load, never transposed);
 // UP: the channel-changing stack-first conv; SAME: everything else.
-#define PPO_CONV_CASE(ALLOWED, CI, CO, HH, WW, TR, MT, NW)                                              \
-    if constexpr (ALLOWED) {                                                                           \
-        if (cin == CI && cout == CO && h == HH && w_ == WW) {                                          \
-            if (t_probe) return PPO_OK;                                                                \
-            return launch_conv<CI, CO, HH, WW, TR, MT, NW, IN_MODE, TRANSPOSED>(in, w, bias, residual, \
-                                                                                 mask_src, out, n, st); \
-        }                                                                                              \
+#define PPO_CONV_CASE(ALLOWED, CI, CO, HH, WW, TR, MT, NW)                             \
+    if constexpr (ALLOWED) {                                                          \
+        if (cin == CI && cout == CO && h == HH && w_ == WW) {                         \
+            if (a.probe) return PPO_OK;                                               \
+            return launch_conv<CI, CO, HH, WW, TR, MT, NW, IN_MODE, TRANSPOSED>(a);   \
+        }                                                                             \
     }
 #ifndef PPO_NW32
 #define PPO_NW32 4
@@ -635,7 +629,7 @@ int dispatch_conv(int cin, int cout, int h, int w_, const void *in, const float 
     PPO_CONV_CASE(SAME, 32, 32, 11, 11, 11, 2, PPO_NW32)   // 121 px = 8 tiles
     PPO_CONV_CASE(SAME, 32, 32, 8, 8, 8, 1, PPO_NW32)      // 64 px = 4 tiles: 1 per wave
 #undef PPO_CONV_CASE
-    if (t_probe) return PPO_E_INVALID;
+    if (a.probe) return PPO_E_INVALID;
     return fail(PPO_E_INVALID, "conv3x3: unsupported geometry cin=%d cout=%d h=%d w=%d transposed=%d", cin,
                 cout, h, w_, (int)TRANSPOSED);
 }
@@ -923,61 +917,53 @@ __global__ __launch_bounds__(NW * 64) void conv3x3_pool_kernel(const void *__res
 }
 
 template <int CIN, int COUT, int H, int W, int PR, int MT, int NW, int IN_MODE, bool PACKED>
-int launch_conv_pool_impl(const void *in, const float *w, const float *bias, float *out, uint8_t *argmax, int n_images,
-                          hipStream_t st)
+int launch_conv_pool_impl(const ConvArgs &a)
 {
     using C = ConvPoolCfg<CIN, COUT, H, W, PR, IN_MODE != IN_U8>;
-    auto kern = conv3x3_pool_kernel<CIN, COUT, H, W, PR, MT, NW, IN_MODE, PACKED>;
+    constexpr auto kern = conv3x3_pool_kernel<CIN, COUT, H, W, PR, MT, NW, IN_MODE, PACKED>;
     constexpr size_t kWeightImage = (size_t)COUT * ((CIN * 9) | 1) * 4;
     constexpr size_t kLdsBytes = C::LDS_BYTES > kWeightImage ? C::LDS_BYTES : kWeightImage;
     static_assert(kLdsBytes <= 160 * 1024, "band + pre-pool rows must fit the 160 KB of LDS");
-    static int wg_per_cu = 0;
-    if (wg_per_cu == 0) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes);
-        if (e != hipSuccess) return fail(PPO_E_HIP, "conv3x3_pool: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        int nb = 0;
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, NW * 64, kLdsBytes);
-        if (e != hipSuccess) return fail(PPO_E_HIP, "conv3x3_pool: occupancy query: %s", hipGetErrorString(e));
-        wg_per_cu = nb < 1 ? 1 : (nb > 3 ? 3 : nb);
-#ifdef PPO_TUNE_CP_WG  // tools/conv_tune experiment build only: force the grid multiple and report what the runtime said
+    int nb = 0;
+    if (int rc = prepare_kernel<kern>("conv3x3_pool", kLdsBytes, NW * 64, &nb)) return rc;
+    int wg_per_cu = nb < 1 ? 1 : (nb > 3 ? 3 : nb);
+#ifdef PPO_TUNE_CP_WG  // tools/conv_tune experiment build only: force the grid multiple and report (once) what the runtime said
+    static bool reported = false;
+    if (!reported)
         fprintf(stderr, "conv3x3_pool<%d,%d,%d>: occupancy query %d workgroups per CU, LDS %zu B; forcing %d\n", CIN, COUT, H, nb,
                 kLdsBytes, PPO_TUNE_CP_WG);
-        wg_per_cu = PPO_TUNE_CP_WG;
+    reported = true;
+    wg_per_cu = PPO_TUNE_CP_WG;
 #endif
-    }
-    const int n_items = n_images * C::NBANDS;
+    const int n_items = a.n * C::NBANDS;
     int grid = 256 * wg_per_cu;
     if (grid > n_items) grid = n_items;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), kLdsBytes, st, in, w, bias, out, argmax, n_images, t_in_index);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), kLdsBytes, a.st, a.in, a.w, a.bias, a.out, a.argmax, a.n, a.in_index);
     return check_launch("conv3x3_pool_kernel");
 }
 
 template <int CIN, int COUT, int H, int W, int PR, int MT, int NW, int IN_MODE>
-int launch_conv_pool(const void *in, const float *w, const float *bias, float *out, uint8_t *argmax, int n_images,
-                     hipStream_t st)
+int launch_conv_pool(const ConvArgs &a)
 {
-    if (t_weights_packed)
-        return launch_conv_pool_impl<CIN, COUT, H, W, PR, MT, NW, IN_MODE, true>(in, w, bias, out, argmax, n_images, st);
-    return launch_conv_pool_impl<CIN, COUT, H, W, PR, MT, NW, IN_MODE, false>(in, w, bias, out, argmax, n_images, st);
+    if (a.packed) return launch_conv_pool_impl<CIN, COUT, H, W, PR, MT, NW, IN_MODE, true>(a);
+    return launch_conv_pool_impl<CIN, COUT, H, W, PR, MT, NW, IN_MODE, false>(a);
 }
 
 template <int IN_MODE>
-int dispatch_conv_pool(int cin, int cout, int h, int w_, const void *in, const float *w, const float *bias, float *out,
-                       uint8_t *argmax, int n, hipStream_t st)
+int dispatch_conv_pool(int cin, int cout, int h, int w_, const ConvArgs &a)
 {
-#define PPO_CP_CASE(ALLOWED, CI, CO, HH, WW, PR, MT, NW)                                                   \
-    if constexpr (ALLOWED) {                                                                                 \
-        if (cin == CI && cout == CO && h == HH && w_ == WW) {                                                \
-            if (t_probe) return PPO_OK;                                                                      \
-            return launch_conv_pool<CI, CO, HH, WW, PR, MT, NW, IN_MODE>(in, w, bias, out, argmax, n, st);  \
-        }                                                                                                    \
+#define PPO_CP_CASE(ALLOWED, CI, CO, HH, WW, PR, MT, NW)                      \
+    if constexpr (ALLOWED) {                                                  \
+        if (cin == CI && cout == CO && h == HH && w_ == WW) {                 \
+            if (a.probe) return PPO_OK;                                       \
+            return launch_conv_pool<CI, CO, HH, WW, PR, MT, NW, IN_MODE>(a);  \
+        }                                                                     \
     }
     constexpr bool FLOAT = IN_MODE == IN_NONE;
     if constexpr (IN_MODE == IN_U8) {
         // (a geometry of the list below: a probe finds it there)
-        if (!t_probe && conv1_pool_supported(cin, cout, h, w_, argmax != nullptr))
-            return conv1_pool_forward(in, t_in_index, w, t_weights_packed != 0, bias, out, argmax, n, cin, h, w_, st);
+        if (!a.probe && conv1_pool_supported(cin, cout, h, w_, a.argmax != nullptr))
+            return conv1_pool_forward(a.in, a.in_index, a.w, a.packed, a.bias, a.out, a.argmax, a.n, cin, h, w_, a.st);
     }
 #ifndef PPO_CP_PR84  // 84x84 first layer: pooled rows per item / pixel tiles per wave group
 #define PPO_CP_PR84 3   // 7 rows x 84 = 37 tiles -> 8 groups of 5; 51 KB of LDS: three workgroups per CU
@@ -1001,9 +987,52 @@ int dispatch_conv_pool(int cin, int cout, int h, int w_, const void *in, const f
     PPO_CP_CASE(FLOAT, 32, 32, 21, 21, PPO_CP_PR21, PPO_CP_MT21, PPO_CP_NW21)
     PPO_CP_CASE(FLOAT, 32, 32, 16, 16, 8, 3, 8)   // 17 rows x 16 = 17 tiles
 #undef PPO_CP_CASE
-    if (t_probe) return PPO_E_INVALID;
+    if (a.probe) return PPO_E_INVALID;
     return fail(PPO_E_INVALID, "conv3x3_pool: unsupported geometry cin=%d cout=%d h=%d w=%d in_mode=%d", cin, cout, h,
                 w_, IN_MODE);
+}
+
+
+// The entry points, each plain form and its packed (and indexed) sibling on one function: `who` is the entry point called.
+int conv_forward(const char *who, bool packed, const void *in, int in_mode, const float *weight, const float *bias,
+                 const float *residual, float *out, int n, int cin, int cout, int h, int w, void *stream)
+{
+    if (n < 0) return fail(PPO_E_INVALID, "%s: n < 0", who);
+    if (n == 0) return PPO_OK;
+    if (!in || !weight || !out) return fail(PPO_E_INVALID, "%s: null pointer", who);
+    ConvArgs a;
+    a.in = in, a.w = weight, a.packed = packed, a.bias = bias, a.residual = residual, a.out = out, a.n = n, a.st = as_stream(stream);
+    const int rc = with_in_mode(in_mode, [&](auto mode) { return dispatch_conv<decltype(mode)::value, false>(cin, cout, h, w, a); });
+    return rc == kNoSuchMode ? fail(PPO_E_INVALID, "%s: unknown in_mode %d", who, in_mode) : rc;
+}
+
+int conv_backward_data(const char *who, bool packed, const float *dy, const float *weight, const float *relu_src,
+                       const float *dres, float *dx, int n, int cin, int cout, int h, int w, void *stream)
+{
+    if (n < 0) return fail(PPO_E_INVALID, "%s: n < 0", who);
+    if (n == 0) return PPO_OK;
+    if (!dy || !weight || !dx) return fail(PPO_E_INVALID, "%s: null pointer", who);
+    ConvArgs a;
+    a.in = dy, a.w = weight, a.packed = packed, a.residual = dres, a.mask_src = relu_src, a.out = dx, a.n = n, a.st = as_stream(stream);
+    // the transposed op contracts over the forward op's output channels
+    return dispatch_conv<IN_NONE, true>(cout, cin, h, w, a);
+}
+
+int conv_pool_forward(const char *who, bool packed, const void *in, const int32_t *index, int in_mode, const float *weight,
+                      const float *bias, float *out, uint8_t *argmax, int n, int cin, int cout, int h, int w, void *stream)
+{
+    if (index && in_mode != IN_U8) return fail(PPO_E_INVALID, "%s: the index applies to uint8 observations", who);
+    if (n < 0) return fail(PPO_E_INVALID, "%s: n < 0", who);
+    if (n == 0) return PPO_OK;
+    if (!in || !weight || !out) return fail(PPO_E_INVALID, "%s: null pointer", who);
+    ConvArgs a;
+    a.in = in, a.in_index = index, a.w = weight, a.packed = packed, a.bias = bias, a.out = out, a.argmax = argmax, a.n = n;
+    a.st = as_stream(stream);
+    const int rc = with_in_mode(in_mode, [&](auto mode) {
+        if constexpr (decltype(mode)::value == IN_RELU) return (int)kNoSuchMode;
+        else return dispatch_conv_pool<decltype(mode)::value>(cin, cout, h, w, a);
+    });
+    return rc == kNoSuchMode ? fail(PPO_E_INVALID, "%s: in_mode %d (the stack-first convolution reads raw input)", who, in_mode) : rc;
 }
 
 }  // namespace
@@ -1013,97 +1042,82 @@ extern "C" int ppo_conv3x3_forward_f32(const void *in, int in_mode, const float 
                                        const float *residual, float *out, int n, int cin, int cout, int h,
                                        int w, void *stream)
 {
-    using namespace ppo;
-    if (n < 0) return fail(PPO_E_INVALID, "ppo_conv3x3_forward_f32: n < 0");
-    if (n == 0) return PPO_OK;
-    if (!in || !weight || !out) return fail(PPO_E_INVALID, "ppo_conv3x3_forward_f32: null pointer");
-    hipStream_t st = as_stream(stream);
-    switch (in_mode) {
-        case IN_NONE: return dispatch_conv<IN_NONE, false>(cin, cout, h, w, in, weight, bias, residual, nullptr, out, n, st);
-        case IN_RELU: return dispatch_conv<IN_RELU, false>(cin, cout, h, w, in, weight, bias, residual, nullptr, out, n, st);
-        case IN_U8: return dispatch_conv<IN_U8, false>(cin, cout, h, w, in, weight, bias, residual, nullptr, out, n, st);
-    }
-    return fail(PPO_E_INVALID, "ppo_conv3x3_forward_f32: unknown in_mode %d", in_mode);
+    return ppo::conv_forward("ppo_conv3x3_forward_f32", false, in, in_mode, weight, bias, residual, out, n, cin, cout, h, w, stream);
+}
+
+extern "C" int ppo_conv3x3_forward_packed_f32(const void *in, int in_mode, const float *packed, const float *bias,
+                                              const float *residual, float *out, int n, int cin, int cout, int h,
+                                              int w, void *stream)
+{
+    return ppo::conv_forward("ppo_conv3x3_forward_packed_f32", true, in, in_mode, packed, bias, residual, out, n, cin, cout, h, w,
+                             stream);
 }
 
 extern "C" int ppo_conv3x3_backward_data_f32(const float *dy, const float *weight, const float *relu_src,
                                              const float *dres, float *dx, int n, int cin, int cout, int h,
                                              int w, void *stream)
 {
-    using namespace ppo;
-    if (n < 0) return fail(PPO_E_INVALID, "ppo_conv3x3_backward_data_f32: n < 0");
-    if (n == 0) return PPO_OK;
-    if (!dy || !weight || !dx) return fail(PPO_E_INVALID, "ppo_conv3x3_backward_data_f32: null pointer");
-    // the transposed op contracts over the forward op's output channels
-    return dispatch_conv<IN_NONE, true>(cout, cin, h, w, dy, weight, nullptr, dres, relu_src, dx, n,
-                                        as_stream(stream));
+    return ppo::conv_backward_data("ppo_conv3x3_backward_data_f32", false, dy, weight, relu_src, dres, dx, n, cin, cout, h, w, stream);
+}
+
+extern "C" int ppo_conv3x3_backward_data_packed_f32(const float *dy, const float *packed, const float *relu_src,
+                                                    const float *dres, float *dx, int n, int cin, int cout, int h,
+                                                    int w, void *stream)
+{
+    return ppo::conv_backward_data("ppo_conv3x3_backward_data_packed_f32", true, dy, packed, relu_src, dres, dx, n, cin, cout, h, w,
+                                   stream);
 }
 
 extern "C" int ppo_conv3x3_pool_forward_f32(const void *in, int in_mode, const float *weight, const float *bias,
                                             float *out, uint8_t *argmax, int n, int cin, int cout, int h, int w,
                                             void *stream)
 {
-    using namespace ppo;
-    if (n < 0) return fail(PPO_E_INVALID, "ppo_conv3x3_pool_forward_f32: n < 0");
-    if (n == 0) return PPO_OK;
-    if (!in || !weight || !out) return fail(PPO_E_INVALID, "ppo_conv3x3_pool_forward_f32: null pointer");
-    hipStream_t st = as_stream(stream);
-    switch (in_mode) {
-        case IN_NONE: return dispatch_conv_pool<IN_NONE>(cin, cout, h, w, in, weight, bias, out, argmax, n, st);
-        case IN_U8: return dispatch_conv_pool<IN_U8>(cin, cout, h, w, in, weight, bias, out, argmax, n, st);
-    }
-    return fail(PPO_E_INVALID, "ppo_conv3x3_pool_forward_f32: in_mode %d (the stack-first convolution reads raw input)", in_mode);
+    return ppo::conv_pool_forward("ppo_conv3x3_pool_forward_f32", false, in, nullptr, in_mode, weight, bias, out, argmax, n, cin, cout,
+                                  h, w, stream);
 }
 
-// The probes: the dispatchers above in no-launch mode.
-extern "C" int ppo_conv3x3_forward_supported(int in_mode, int cin, int cout, int h, int w)
+extern "C" int ppo_conv3x3_pool_forward_packed_f32(const void *in, int in_mode, const float *packed, const float *bias,
+                                                   float *out, uint8_t *argmax, int n, int cin, int cout, int h,
+                                                   int w, void *stream)
 {
-    using namespace ppo;
-    t_probe = 1;
-    int rc = PPO_E_INVALID;
-    switch (in_mode) {
-        case IN_NONE: rc = dispatch_conv<IN_NONE, false>(cin, cout, h, w, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, nullptr); break;
-        case IN_RELU: rc = dispatch_conv<IN_RELU, false>(cin, cout, h, w, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, nullptr); break;
-        case IN_U8: rc = dispatch_conv<IN_U8, false>(cin, cout, h, w, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, nullptr); break;
-    }
-    t_probe = 0;
-    return rc == PPO_OK ? 1 : 0;
-}
-
-extern "C" int ppo_conv3x3_backward_data_supported(int cin, int cout, int h, int w)
-{
-    using namespace ppo;
-    t_probe = 1;
-    const int rc = dispatch_conv<IN_NONE, true>(cout, cin, h, w, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, nullptr);
-    t_probe = 0;
-    return rc == PPO_OK ? 1 : 0;
-}
-
-extern "C" int ppo_conv3x3_pool_forward_supported(int in_mode, int cin, int cout, int h, int w)
-{
-    using namespace ppo;
-    t_probe = 1;
-    int rc = PPO_E_INVALID;
-    switch (in_mode) {
-        case IN_NONE: rc = dispatch_conv_pool<IN_NONE>(cin, cout, h, w, nullptr, nullptr, nullptr, nullptr, nullptr, 1, nullptr); break;
-        case IN_U8: rc = dispatch_conv_pool<IN_U8>(cin, cout, h, w, nullptr, nullptr, nullptr, nullptr, nullptr, 1, nullptr); break;
-    }
-    t_probe = 0;
-    return rc == PPO_OK ? 1 : 0;
+    return ppo::conv_pool_forward("ppo_conv3x3_pool_forward_packed_f32", true, in, nullptr, in_mode, packed, bias, out, argmax, n, cin,
+                                  cout, h, w, stream);
 }
 
 extern "C" int ppo_conv3x3_pool_forward_packed_indexed_f32(const void *in, const int32_t *index, int in_mode, const float *packed,
                                                            const float *bias, float *out, uint8_t *argmax, int n, int cin,
                                                            int cout, int h, int w, void *stream)
 {
-    if (index && in_mode != ppo::IN_U8)
-        return ppo::fail(PPO_E_INVALID, "ppo_conv3x3_pool_forward_packed_indexed_f32: the index applies to uint8 observations");
-    ppo::t_weights_packed = 1;
-    ppo::t_in_index = index;
-    const int rc = ppo_conv3x3_pool_forward_f32(in, in_mode, packed, bias, out, argmax, n, cin, cout, h, w, stream);
-    ppo::t_in_index = nullptr;
-    ppo::t_weights_packed = 0;
-    return rc;
+    return ppo::conv_pool_forward("ppo_conv3x3_pool_forward_packed_indexed_f32", true, in, index, in_mode, packed, bias, out, argmax,
+                                  n, cin, cout, h, w, stream);
+}
+
+// The probes: the dispatchers above in no-launch mode.
+extern "C" int ppo_conv3x3_forward_supported(int in_mode, int cin, int cout, int h, int w)
+{
+    using namespace ppo;
+    ConvArgs probe;
+    probe.probe = true;
+    return with_in_mode(in_mode, [&](auto mode) { return dispatch_conv<decltype(mode)::value, false>(cin, cout, h, w, probe); }) == PPO_OK;
+}
+
+extern "C" int ppo_conv3x3_backward_data_supported(int cin, int cout, int h, int w)
+{
+    using namespace ppo;
+    ConvArgs probe;
+    probe.probe = true;
+    return dispatch_conv<IN_NONE, true>(cout, cin, h, w, probe) == PPO_OK;
+}
+
+extern "C" int ppo_conv3x3_pool_forward_supported(int in_mode, int cin, int cout, int h, int w)
+{
+    using namespace ppo;
+    ConvArgs probe;
+    probe.probe = true;
+    return with_in_mode(in_mode, [&](auto mode) {
+        if constexpr (decltype(mode)::value == IN_RELU) return (int)kNoSuchMode;
+        else return dispatch_conv_pool<decltype(mode)::value>(cin, cout, h, w, probe);
+    }) == PPO_OK;
 }
 
 extern "C" size_t ppo_conv3x3_packed_floats(int cin, int cout, int transposed)
@@ -1125,34 +1139,4 @@ extern "C" int ppo_conv3x3_pack_weights_f32(const ppo_pack_job *jobs, int n_jobs
     }
     hipLaunchKernelGGL(pack_weights_kernel, dim3(40, n_jobs), dim3(256), 0, as_stream(stream), pj);
     return check_launch("pack_weights_kernel");
-}
-
-extern "C" int ppo_conv3x3_forward_packed_f32(const void *in, int in_mode, const float *packed, const float *bias,
-                                              const float *residual, float *out, int n, int cin, int cout, int h,
-                                              int w, void *stream)
-{
-    ppo::t_weights_packed = 1;
-    const int rc = ppo_conv3x3_forward_f32(in, in_mode, packed, bias, residual, out, n, cin, cout, h, w, stream);
-    ppo::t_weights_packed = 0;
-    return rc;
-}
-
-extern "C" int ppo_conv3x3_backward_data_packed_f32(const float *dy, const float *packed, const float *relu_src,
-                                                    const float *dres, float *dx, int n, int cin, int cout, int h,
-                                                    int w, void *stream)
-{
-    ppo::t_weights_packed = 1;
-    const int rc = ppo_conv3x3_backward_data_f32(dy, packed, relu_src, dres, dx, n, cin, cout, h, w, stream);
-    ppo::t_weights_packed = 0;
-    return rc;
-}
-
-extern "C" int ppo_conv3x3_pool_forward_packed_f32(const void *in, int in_mode, const float *packed, const float *bias,
-                                                   float *out, uint8_t *argmax, int n, int cin, int cout, int h,
-                                                   int w, void *stream)
-{
-    ppo::t_weights_packed = 1;
-    const int rc = ppo_conv3x3_pool_forward_f32(in, in_mode, packed, bias, out, argmax, n, cin, cout, h, w, stream);
-    ppo::t_weights_packed = 0;
-    return rc;
 }

@@ -238,17 +238,10 @@ int launch_block(const float *in, const float *w0, const float *b0, const float 
                  hipStream_t st)
 {
     using S = BlockCfg<C, H, W, TR, NW>;
-    auto kern = conv3x3_block_kernel<C, H, W, TR, NW>;
-    static int wg_per_cu = 0;
-    if (wg_per_cu == 0) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)S::LDS_BYTES);
-        if (e != hipSuccess) return fail(PPO_E_HIP, "conv3x3_block: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        int nb = 0;
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, NW * 64, S::LDS_BYTES);
-        if (e != hipSuccess) return fail(PPO_E_HIP, "conv3x3_block: occupancy query: %s", hipGetErrorString(e));
-        wg_per_cu = nb < 1 ? 1 : (nb > 3 ? 3 : nb);
-    }
+    constexpr auto kern = conv3x3_block_kernel<C, H, W, TR, NW>;
+    int nb = 0;
+    if (int rc = prepare_kernel<kern>("conv3x3_block", S::LDS_BYTES, NW * 64, &nb)) return rc;
+    const int wg_per_cu = nb < 1 ? 1 : (nb > 3 ? 3 : nb);
     const int n_items = n * S::NBANDS;
     int grid = 256 * wg_per_cu;
     if (grid > n_items) grid = n_items;

@@ -207,11 +207,6 @@ __device__ __forceinline__ void wgrad_k_loops(const float *__restrict__ s_x, con
 // Up to kWgradBatch independent problems of one geometry per launch (blockIdx.y picks one): the layers of a stack share
 // their geometry and their gradients are all known once its backward-data pass is through, and one launch of 4 x the
 // workgroups has one ramp and one tail where four launches have four (per-launch constant ~10 us).
-// set by ppo_conv3x3_backward_weight_slabs_pooled_indexed_f32 around its dispatch (see WgradBatch::in_index)
-thread_local const int32_t *t_wgrad_in_index = nullptr;
-// dispatch_wgrad answers "is there a kernel" instead of launching it (ppo_conv3x3_backward_weight_supported): one case
-// list serves both
-thread_local int t_wgrad_probe = 0;
 constexpr int kWgradBatch = 5;  // a stack's four block convolutions + the next stack's first convolution (same geometry)
 struct WgradBatch {
     const void *in[kWgradBatch];
@@ -591,21 +586,34 @@ __global__ __launch_bounds__(256) void conv3x3_wgrad_reduce_jobs_kernel(ReduceJo
     }
 }
 
+// One call of dispatch_wgrad, handed from the entry point through it to launch_wgrad.
+struct WgradArgs {
+    // answer "is there a kernel" (PPO_OK / PPO_E_INVALID) instead of launching it (ppo_conv3x3_backward_weight_supported,
+    // which fills in nothing else): one case list serves both
+    bool probe = false;
+    const void *in = nullptr;
+    const float *dy = nullptr;           // with argmax: the POOLED gradient (WgradBatch::dy)
+    float *dw = nullptr, *db = nullptr;  // where the call reduces its slabs itself (n_slabs_out == nullptr); db nullable
+    float *ws = nullptr;
+    size_t ws_bytes = 0;
+    int n = 0;
+    int accumulate = 0;
+    int *n_slabs_out = nullptr;          // slabs only: the caller reduces them later (ppo_conv3x3_wgrad_reduce_f32)
+    const WgradBatch *more = nullptr;    // `count` problems of one geometry, each with a workspace of ws_bytes
+    int count = 1;
+    const uint8_t *argmax = nullptr;     // the pooled-gradient kernels (WgradBatch::argmax)
+    const int32_t *in_index = nullptr;   // uint8 input only, nullable (WgradBatch::in_index)
+    hipStream_t st = nullptr;
+};
+
 template <int CIN, int COUT, int H, int W, int TR, int IN_MODE, bool DY_POOLED = false>
-int launch_wgrad(const void *in, const float *dy, float *dw, float *db, float *workspace, size_t workspace_bytes,
-                 int n_images, int accumulate, hipStream_t st, int *n_slabs_out = nullptr,
-                 const WgradBatch *more = nullptr, int count = 1, const uint8_t *argmax = nullptr)
+int launch_wgrad(const WgradArgs &a)
 {
     using C = WgradCfg<CIN, COUT, H, W, TR, wgrad_nbuf<IN_MODE, (H + TR - 1) / TR>(), wgrad_run<IN_MODE, DY_POOLED>()>;
-    auto kern = conv3x3_wgrad_kernel<CIN, COUT, H, W, TR, IN_MODE, DY_POOLED>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS_BYTES);
-        if (e != hipSuccess) return fail(PPO_E_HIP, "conv3x3_wgrad: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr_set = true;
-    }
-    const int n_items = n_images * C::NBANDS;
+    constexpr auto kern = conv3x3_wgrad_kernel<CIN, COUT, H, W, TR, IN_MODE, DY_POOLED>;
+    if (int rc = prepare_kernel<kern>("conv3x3_wgrad", C::LDS_BYTES)) return rc;
+    const int count = a.count;
+    const int n_items = a.n * C::NBANDS;
     // as many workgroups as fit on the chip at once (LDS-limited), at most kWgradMaxSlabs slabs
     int per_cu = (int)((160 * 1024) / C::LDS_BYTES);
     per_cu = per_cu < 1 ? 1 : (per_cu > PPO_TUNE_WGRAD_PERCU ? PPO_TUNE_WGRAD_PERCU : per_cu);
@@ -621,57 +629,53 @@ int launch_wgrad(const void *in, const float *dy, float *dw, float *db, float *w
     if (grid > kWgradMaxSlabs) grid = kWgradMaxSlabs;
     if (grid > n_items) grid = n_items;
     const size_t need = (size_t)grid * COUT * C::JP * sizeof(float);
-    if (need > workspace_bytes)
-        return fail(PPO_E_INVALID, "conv3x3_wgrad: workspace too small (%zu < %zu bytes)", workspace_bytes, need);
+    if (need > a.ws_bytes)
+        return fail(PPO_E_INVALID, "conv3x3_wgrad: workspace too small (%zu < %zu bytes)", a.ws_bytes, need);
     WgradBatch batch{};
-    if (more) {
-        batch = *more;  // `count` problems, each with a workspace of workspace_bytes
+    if (a.more) {
+        batch = *a.more;
     } else {
-        batch.in[0] = in;
-        batch.dy[0] = dy;
-        batch.partial[0] = workspace;
+        batch.in[0] = a.in;
+        batch.dy[0] = a.dy;
+        batch.partial[0] = a.ws;
     }
-    batch.argmax = argmax;
-    batch.in_index = IN_MODE == IN_U8 ? t_wgrad_in_index : nullptr;
-    hipLaunchKernelGGL(kern, dim3(grid, count), dim3(wgrad_threads<IN_MODE, C::NBANDS, DY_POOLED>()), C::LDS_BYTES, st, batch,
-                       n_images);
+    batch.argmax = a.argmax;
+    batch.in_index = IN_MODE == IN_U8 ? a.in_index : nullptr;
+    hipLaunchKernelGGL(kern, dim3(grid, count), dim3(wgrad_threads<IN_MODE, C::NBANDS, DY_POOLED>()), C::LDS_BYTES, a.st, batch,
+                       a.n);
     int rc = check_launch("conv3x3_wgrad_kernel");
     if (rc) return rc;
-    if (n_slabs_out) {  // slabs only: the caller reduces later (ppo_conv3x3_wgrad_reduce_f32)
-        *n_slabs_out = grid;
+    if (a.n_slabs_out) {
+        *a.n_slabs_out = grid;
         return PPO_OK;
     }
     const int total = COUT * (C::JP / 4);  // one thread quad-group per 4 consecutive j
-    hipLaunchKernelGGL(conv3x3_wgrad_reduce_kernel, dim3((total + 15) / 16), dim3(256), 0, st, workspace, grid, COUT,
-                       CIN, C::CINP, C::JP, dw, db, accumulate);
+    hipLaunchKernelGGL(conv3x3_wgrad_reduce_kernel, dim3((total + 15) / 16), dim3(256), 0, a.st, a.ws, grid, COUT,
+                       CIN, C::CINP, C::JP, a.dw, a.db, a.accumulate);
     return check_launch("conv3x3_wgrad_reduce_kernel");
 }
 
 template <int IN_MODE>
-int dispatch_wgrad(int cin, int cout, int h, int w_, const void *in, const float *dy, float *dw, float *db,
-                   float *ws, size_t ws_bytes, int n, int accumulate, hipStream_t st, int *n_slabs_out = nullptr,
-                   const WgradBatch *more = nullptr, int count = 1, const uint8_t *argmax = nullptr)
+int dispatch_wgrad(int cin, int cout, int h, int w_, const WgradArgs &a)
 {
 #define PPO_WGRAD_POOLED_CASE(CI, CO, HH, WW, TR)                                                    \
     if constexpr (IN_MODE != IN_RELU) {                                                              \
-        if (argmax && cin == CI && cout == CO && h == HH && w_ == WW)                                \
-            return launch_wgrad<CI, CO, HH, WW, TR, IN_MODE, true>(in, dy, dw, db, ws, ws_bytes, n, accumulate, st, n_slabs_out, \
-                                                                   nullptr, 1, argmax);              \
+        if (a.argmax && cin == CI && cout == CO && h == HH && w_ == WW)                              \
+            return launch_wgrad<CI, CO, HH, WW, TR, IN_MODE, true>(a);                               \
     }
     PPO_WGRAD_POOLED_CASE(4, 16, 84, 84, 6)
     PPO_WGRAD_POOLED_CASE(5, 16, 84, 84, 6)
     PPO_WGRAD_POOLED_CASE(3, 16, 64, 64, 8)
     PPO_WGRAD_POOLED_CASE(4, 16, 64, 64, 8)
 #undef PPO_WGRAD_POOLED_CASE
-    if (argmax)
+    if (a.argmax)
         return fail(PPO_E_INVALID, "conv3x3_wgrad: no pooled-gradient kernel for cin=%d cout=%d h=%d w=%d in_mode=%d", cin,
                     cout, h, w_, IN_MODE);
 #define PPO_WGRAD_CASE(ALLOWED, CI, CO, HH, WW, TR)                                                  \
     if constexpr (ALLOWED) {                                                                         \
         if (cin == CI && cout == CO && h == HH && w_ == WW) {                                        \
-            if (t_wgrad_probe) return PPO_OK;                                                        \
-            return launch_wgrad<CI, CO, HH, WW, TR, IN_MODE>(in, dy, dw, db, ws, ws_bytes, n, accumulate, st, n_slabs_out, \
-                                                             more, count);                                   \
+            if (a.probe) return PPO_OK;                                                              \
+            return launch_wgrad<CI, CO, HH, WW, TR, IN_MODE>(a);                                     \
         }                                                                                            \
     }
     constexpr bool FIRST = IN_MODE != IN_RELU;
@@ -692,9 +696,32 @@ int dispatch_wgrad(int cin, int cout, int h, int w_, const void *in, const float
     PPO_WGRAD_CASE(SAME, 32, 32, 11, 11, 11)
     PPO_WGRAD_CASE(SAME, 32, 32, 8, 8, 8)
 #undef PPO_WGRAD_CASE
-    if (t_wgrad_probe) return PPO_E_INVALID;
+    if (a.probe) return PPO_E_INVALID;
     return fail(PPO_E_INVALID, "conv3x3_wgrad: unsupported geometry cin=%d cout=%d h=%d w=%d in_mode=%d", cin, cout,
                 h, w_, IN_MODE);
+}
+
+// dispatch_wgrad for a run-time in_mode: kNoSuchMode for a value that is none
+int dispatch_wgrad_mode(int in_mode, int cin, int cout, int h, int w, const WgradArgs &a)
+{
+    return with_in_mode(in_mode, [&](auto mode) { return dispatch_wgrad<decltype(mode)::value>(cin, cout, h, w, a); });
+}
+
+// ppo_conv3x3_backward_weight_slabs_pooled_f32 and its indexed sibling: `who` is the entry point called
+int wgrad_slabs_pooled(const char *who, const void *in, const int32_t *index, int in_mode, const float *g, const uint8_t *argmax,
+                       void *workspace, size_t workspace_bytes, int n, int cin, int cout, int h, int w, int *n_slabs, void *stream)
+{
+    if (index && in_mode != IN_U8) return fail(PPO_E_INVALID, "%s: the index applies to uint8 observations", who);
+    if (n <= 0) return fail(PPO_E_INVALID, "%s: n must be positive", who);
+    if (!in || !g || !argmax || !workspace || !n_slabs) return fail(PPO_E_INVALID, "%s: null pointer", who);
+    WgradArgs a;
+    a.in = in, a.in_index = index, a.dy = g, a.argmax = argmax, a.n = n, a.n_slabs_out = n_slabs, a.st = as_stream(stream);
+    a.ws = static_cast<float *>(workspace), a.ws_bytes = workspace_bytes;
+    const int rc = with_in_mode(in_mode, [&](auto mode) {
+        if constexpr (decltype(mode)::value == IN_RELU) return (int)kNoSuchMode;
+        else return dispatch_wgrad<decltype(mode)::value>(cin, cout, h, w, a);
+    });
+    return rc == kNoSuchMode ? fail(PPO_E_INVALID, "%s: in_mode %d has no pooled-gradient kernel", who, in_mode) : rc;
 }
 
 }  // namespace
@@ -714,29 +741,19 @@ extern "C" int ppo_conv3x3_backward_weight_f32(const void *in, int in_mode, cons
     using namespace ppo;
     if (n <= 0) return fail(PPO_E_INVALID, "ppo_conv3x3_backward_weight_f32: n must be positive");
     if (!in || !dy || !dweight || !workspace) return fail(PPO_E_INVALID, "ppo_conv3x3_backward_weight_f32: null pointer");
-    hipStream_t st = as_stream(stream);
-    float *ws = static_cast<float *>(workspace);
-    switch (in_mode) {
-        case IN_NONE: return dispatch_wgrad<IN_NONE>(cin, cout, h, w, in, dy, dweight, dbias, ws, workspace_bytes, n, accumulate, st);
-        case IN_RELU: return dispatch_wgrad<IN_RELU>(cin, cout, h, w, in, dy, dweight, dbias, ws, workspace_bytes, n, accumulate, st);
-        case IN_U8: return dispatch_wgrad<IN_U8>(cin, cout, h, w, in, dy, dweight, dbias, ws, workspace_bytes, n, accumulate, st);
-    }
-    return fail(PPO_E_INVALID, "ppo_conv3x3_backward_weight_f32: unknown in_mode %d", in_mode);
+    WgradArgs a;
+    a.in = in, a.dy = dy, a.dw = dweight, a.db = dbias, a.n = n, a.accumulate = accumulate, a.st = as_stream(stream);
+    a.ws = static_cast<float *>(workspace), a.ws_bytes = workspace_bytes;
+    const int rc = dispatch_wgrad_mode(in_mode, cin, cout, h, w, a);
+    return rc == kNoSuchMode ? fail(PPO_E_INVALID, "ppo_conv3x3_backward_weight_f32: unknown in_mode %d", in_mode) : rc;
 }
 
 // The probe: dispatch_wgrad in no-launch mode (the plain, slab and batched forms share its case list).
 extern "C" int ppo_conv3x3_backward_weight_supported(int in_mode, int cin, int cout, int h, int w)
 {
-    using namespace ppo;
-    t_wgrad_probe = 1;
-    int rc = PPO_E_INVALID;
-    switch (in_mode) {
-        case IN_NONE: rc = dispatch_wgrad<IN_NONE>(cin, cout, h, w, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 1, 0, nullptr); break;
-        case IN_RELU: rc = dispatch_wgrad<IN_RELU>(cin, cout, h, w, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 1, 0, nullptr); break;
-        case IN_U8: rc = dispatch_wgrad<IN_U8>(cin, cout, h, w, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 1, 0, nullptr); break;
-    }
-    t_wgrad_probe = 0;
-    return rc == PPO_OK ? 1 : 0;
+    ppo::WgradArgs probe;
+    probe.probe = true;
+    return ppo::dispatch_wgrad_mode(in_mode, cin, cout, h, w, probe) == PPO_OK;
 }
 
 extern "C" int ppo_conv3x3_backward_weight_slabs_f32(const void *in, int in_mode, const float *dy, void *workspace,
@@ -746,14 +763,11 @@ extern "C" int ppo_conv3x3_backward_weight_slabs_f32(const void *in, int in_mode
     using namespace ppo;
     if (n <= 0) return fail(PPO_E_INVALID, "ppo_conv3x3_backward_weight_slabs_f32: n must be positive");
     if (!in || !dy || !workspace || !n_slabs) return fail(PPO_E_INVALID, "ppo_conv3x3_backward_weight_slabs_f32: null pointer");
-    hipStream_t st = as_stream(stream);
-    float *ws = static_cast<float *>(workspace);
-    switch (in_mode) {
-        case IN_NONE: return dispatch_wgrad<IN_NONE>(cin, cout, h, w, in, dy, nullptr, nullptr, ws, workspace_bytes, n, 0, st, n_slabs);
-        case IN_RELU: return dispatch_wgrad<IN_RELU>(cin, cout, h, w, in, dy, nullptr, nullptr, ws, workspace_bytes, n, 0, st, n_slabs);
-        case IN_U8: return dispatch_wgrad<IN_U8>(cin, cout, h, w, in, dy, nullptr, nullptr, ws, workspace_bytes, n, 0, st, n_slabs);
-    }
-    return fail(PPO_E_INVALID, "ppo_conv3x3_backward_weight_slabs_f32: unknown in_mode %d", in_mode);
+    WgradArgs a;
+    a.in = in, a.dy = dy, a.n = n, a.n_slabs_out = n_slabs, a.st = as_stream(stream);
+    a.ws = static_cast<float *>(workspace), a.ws_bytes = workspace_bytes;
+    const int rc = dispatch_wgrad_mode(in_mode, cin, cout, h, w, a);
+    return rc == kNoSuchMode ? fail(PPO_E_INVALID, "ppo_conv3x3_backward_weight_slabs_f32: unknown in_mode %d", in_mode) : rc;
 }
 
 extern "C" int ppo_conv3x3_backward_weight_slabs_batch_f32(const void *const *ins, int in_mode, const float *const *dys,
@@ -774,14 +788,10 @@ extern "C" int ppo_conv3x3_backward_weight_slabs_batch_f32(const void *const *in
         b.dy[k] = dys[k];
         b.partial[k] = static_cast<float *>(workspaces[k]);
     }
-    hipStream_t st = as_stream(stream);
-    float *ws = b.partial[0];
-    switch (in_mode) {
-        case IN_NONE: return dispatch_wgrad<IN_NONE>(cin, cout, h, w, b.in[0], b.dy[0], nullptr, nullptr, ws, workspace_bytes, n, 0, st, n_slabs, &b, count);
-        case IN_RELU: return dispatch_wgrad<IN_RELU>(cin, cout, h, w, b.in[0], b.dy[0], nullptr, nullptr, ws, workspace_bytes, n, 0, st, n_slabs, &b, count);
-        case IN_U8: return dispatch_wgrad<IN_U8>(cin, cout, h, w, b.in[0], b.dy[0], nullptr, nullptr, ws, workspace_bytes, n, 0, st, n_slabs, &b, count);
-    }
-    return fail(PPO_E_INVALID, "ppo_conv3x3_backward_weight_slabs_batch_f32: unknown in_mode %d", in_mode);
+    WgradArgs a;
+    a.more = &b, a.count = count, a.ws_bytes = workspace_bytes, a.n = n, a.n_slabs_out = n_slabs, a.st = as_stream(stream);
+    const int rc = dispatch_wgrad_mode(in_mode, cin, cout, h, w, a);
+    return rc == kNoSuchMode ? fail(PPO_E_INVALID, "ppo_conv3x3_backward_weight_slabs_batch_f32: unknown in_mode %d", in_mode) : rc;
 }
 
 extern "C" int ppo_conv3x3_backward_weight_slabs_batch_mixed_f32(const void *const *ins, const int *relu, const float *const *dys,
@@ -803,8 +813,9 @@ extern "C" int ppo_conv3x3_backward_weight_slabs_batch_mixed_f32(const void *con
         b.partial[k] = static_cast<float *>(workspaces[k]);
         b.relu_floor[k] = relu[k] ? 0.f : -__builtin_inff();
     }
-    return dispatch_wgrad<IN_RELU>(cin, cout, h, w, b.in[0], b.dy[0], nullptr, nullptr, b.partial[0], workspace_bytes, n, 0,
-                                   as_stream(stream), n_slabs, &b, count);
+    WgradArgs a;
+    a.more = &b, a.count = count, a.ws_bytes = workspace_bytes, a.n = n, a.n_slabs_out = n_slabs, a.st = as_stream(stream);
+    return dispatch_wgrad<IN_RELU>(cin, cout, h, w, a);
 }
 
 extern "C" int ppo_conv3x3_backward_weight_slabs_pooled_f32(const void *in, int in_mode, const float *g,
@@ -812,17 +823,8 @@ extern "C" int ppo_conv3x3_backward_weight_slabs_pooled_f32(const void *in, int 
                                                             int n, int cin, int cout, int h, int w, int *n_slabs,
                                                             void *stream)
 {
-    using namespace ppo;
-    if (n <= 0) return fail(PPO_E_INVALID, "ppo_conv3x3_backward_weight_slabs_pooled_f32: n must be positive");
-    if (!in || !g || !argmax || !workspace || !n_slabs)
-        return fail(PPO_E_INVALID, "ppo_conv3x3_backward_weight_slabs_pooled_f32: null pointer");
-    hipStream_t st = as_stream(stream);
-    float *ws = static_cast<float *>(workspace);
-    switch (in_mode) {
-        case IN_NONE: return dispatch_wgrad<IN_NONE>(cin, cout, h, w, in, g, nullptr, nullptr, ws, workspace_bytes, n, 0, st, n_slabs, nullptr, 1, argmax);
-        case IN_U8: return dispatch_wgrad<IN_U8>(cin, cout, h, w, in, g, nullptr, nullptr, ws, workspace_bytes, n, 0, st, n_slabs, nullptr, 1, argmax);
-    }
-    return fail(PPO_E_INVALID, "ppo_conv3x3_backward_weight_slabs_pooled_f32: in_mode %d has no pooled-gradient kernel", in_mode);
+    return ppo::wgrad_slabs_pooled("ppo_conv3x3_backward_weight_slabs_pooled_f32", in, nullptr, in_mode, g, argmax, workspace,
+                                   workspace_bytes, n, cin, cout, h, w, n_slabs, stream);
 }
 
 extern "C" int ppo_conv3x3_backward_weight_slabs_pooled_indexed_f32(const void *in, const int32_t *index, int in_mode,
@@ -830,13 +832,8 @@ extern "C" int ppo_conv3x3_backward_weight_slabs_pooled_indexed_f32(const void *
                                                                     size_t workspace_bytes, int n, int cin, int cout, int h,
                                                                     int w, int *n_slabs, void *stream)
 {
-    if (index && in_mode != ppo::IN_U8)
-        return ppo::fail(PPO_E_INVALID, "ppo_conv3x3_backward_weight_slabs_pooled_indexed_f32: the index applies to uint8 observations");
-    ppo::t_wgrad_in_index = index;
-    const int rc = ppo_conv3x3_backward_weight_slabs_pooled_f32(in, in_mode, g, argmax, workspace, workspace_bytes, n, cin, cout, h,
-                                                                w, n_slabs, stream);
-    ppo::t_wgrad_in_index = nullptr;
-    return rc;
+    return ppo::wgrad_slabs_pooled("ppo_conv3x3_backward_weight_slabs_pooled_indexed_f32", in, index, in_mode, g, argmax, workspace,
+                                   workspace_bytes, n, cin, cout, h, w, n_slabs, stream);
 }
 
 extern "C" int ppo_conv3x3_backward_weight_pooled_supported(int cin, int cout, int h, int w)

@@ -304,17 +304,11 @@ template <int CI, int CO, int H, int W, int TR, bool POOL = false, int NS = 2>
 int launch_split_conv(const SplitConvArgs &args, hipStream_t st)
 {
     using C = SplitConvCfg<CI, CO, H, W, TR, POOL, NS>;
-    auto kern = conv3x3_bf16x3_kernel<CI, CO, H, W, TR, POOL, NS>;
-    static int per_cu = 0;
-    if (!per_cu) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)C::LDS_BYTES);
-        if (e != hipSuccess) return fail(PPO_E_HIP, "conv3x3_bf16x3: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        int occ = 0;
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, reinterpret_cast<const void *>(kern), kConvWaves * 64, C::LDS_BYTES);
-        if (e != hipSuccess || occ < 1) return fail(PPO_E_HIP, "conv3x3_bf16x3: occupancy query: %s", hipGetErrorString(e));
-        per_cu = occ > 4 ? 4 : occ;
-    }
+    constexpr auto kern = conv3x3_bf16x3_kernel<CI, CO, H, W, TR, POOL, NS>;
+    int occ = 0;
+    if (int rc = prepare_kernel<kern>("conv3x3_bf16x3", C::LDS_BYTES, kConvWaves * 64, &occ)) return rc;
+    if (occ < 1) return fail(PPO_E_HIP, "conv3x3_bf16x3: occupancy query: %s", hipGetErrorString(hipSuccess));
+    const int per_cu = occ > 4 ? 4 : occ;
     const int n_items = args.n_images * C::NB;
     const int grid = n_items < 256 * per_cu ? n_items : 256 * per_cu;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(kConvWaves * 64), C::LDS_BYTES, st, args);

@@ -13,10 +13,26 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <type_traits>
 
 namespace ppo {
 
 enum { IN_NONE = 0, IN_RELU = 1, IN_U8 = 2 };
+
+// A run-time in_mode as a template argument: f(std::integral_constant<int, MODE>{}) for the mode of this call, or
+// kNoSuchMode for a value that is no mode.  An entry point that refuses one of the modes returns kNoSuchMode from f for it
+// (under `if constexpr`, so that no kernel of that mode is instantiated); the entry point words the error itself.
+constexpr int kNoSuchMode = 1;  // no PPO_* code: those are <= 0
+template <class F>
+int with_in_mode(int in_mode, F &&f)
+{
+    switch (in_mode) {
+        case IN_NONE: return f(std::integral_constant<int, IN_NONE>{});
+        case IN_RELU: return f(std::integral_constant<int, IN_RELU>{});
+        case IN_U8: return f(std::integral_constant<int, IN_U8>{});
+    }
+    return kNoSuchMode;
+}
 
 // uint8 observation -> x / 255 (rl/models.py:842-848: x.float() / 255), bit for bit the IEEE quotient for every one of
 // the 256 inputs, as a multiply and two fused multiply-adds instead of the ~10-instruction division sequence:

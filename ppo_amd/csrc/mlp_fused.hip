@@ -519,13 +519,7 @@ int launch_rows(MlpArgs &a, hipStream_t st)
     const size_t lds = mlp_lds_bytes(a.F, a.H, a.NH, a.loss != MLP_LOSS_NONE);
     a.lds_floats = (int)(lds / 4) - kMlpWaves * 64;
     if (lds > 160 * 1024) return fail(PPO_E_INVALID, "mlp_rows: a tile of %d features / %d hidden / %d heads needs %zu bytes of LDS", a.F, a.H, a.NH, lds);
-    static bool ready = false;
-    if (!ready) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(mlp_rows_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return fail(PPO_E_HIP, "mlp_rows: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        ready = true;
-    }
+    if (int rc = prepare_kernel<mlp_rows_kernel>("mlp_rows", 160 * 1024)) return rc;
     hipLaunchKernelGGL(mlp_rows_kernel, dim3((a.B + kRows - 1) / kRows), dim3(kMlpThreads), lds, st, a);
     return check_launch("mlp_rows_kernel");
 }

@@ -452,14 +452,8 @@ template <int C, int H, int W, int MT, int NW, bool BACKWARD>
 int launch_split_tail(const SplitTailArgs &args, hipStream_t st)
 {
     using S = SplitCfg<C, H, W, MT, NW>;
-    auto kern = stack_tail_bf16x3_kernel<C, H, W, MT, NW, BACKWARD>;
-    static bool ready = false;
-    if (!ready) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)S::LDS_BYTES);
-        if (e != hipSuccess) return fail(PPO_E_HIP, "stack_tail_bf16x3: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        ready = true;
-    }
+    constexpr auto kern = stack_tail_bf16x3_kernel<C, H, W, MT, NW, BACKWARD>;
+    if (int rc = prepare_kernel<kern>("stack_tail_bf16x3", S::LDS_BYTES)) return rc;
     int grid = args.n_images < 256 ? args.n_images : 256;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(S::WAVES * 64), S::LDS_BYTES, st, args);
     return check_launch("stack_tail_bf16x3_kernel");
@@ -469,14 +463,8 @@ template <int HI, int W, int NWIN, int R, int NW, int MT, bool BACKWARD>
 int launch_split_win16(const SplitTailArgs &args, hipStream_t st)
 {
     using S = Split16Cfg<HI, W, NWIN, R, NW, MT>;
-    auto kern = stack_win16_bf16x3_kernel<HI, W, NWIN, R, NW, MT, BACKWARD>;
-    static bool ready = false;
-    if (!ready) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)S::LDS_BYTES);
-        if (e != hipSuccess) return fail(PPO_E_HIP, "stack_win16_bf16x3: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        ready = true;
-    }
+    constexpr auto kern = stack_win16_bf16x3_kernel<HI, W, NWIN, R, NW, MT, BACKWARD>;
+    if (int rc = prepare_kernel<kern>("stack_win16_bf16x3", S::LDS_BYTES)) return rc;
     const int items = args.n_images * NWIN;
     const int per_cu = S::LDS_BYTES <= 80 * 1024 ? 2 : 1;
     const int grid = items < 256 * per_cu ? items : 256 * per_cu;

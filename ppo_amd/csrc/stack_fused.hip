@@ -250,17 +250,10 @@ template <int C, int H, int W, int MT, int NW, int NSPLIT, bool BACKWARD>
 int launch_stack_tail(const StackTailArgs &args, hipStream_t st)
 {
     using S = StackCfg<C, H, W, MT, NW, NSPLIT>;
-    auto kern = stack_tail_kernel<C, H, W, MT, NW, NSPLIT, BACKWARD>;
-    static int wg_per_cu = 0;
-    if (wg_per_cu == 0) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)S::LDS_BYTES);
-        if (e != hipSuccess) return fail(PPO_E_HIP, "stack_tail: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        int nb = 0;
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, S::WAVES * 64, S::LDS_BYTES);
-        if (e != hipSuccess) return fail(PPO_E_HIP, "stack_tail: occupancy query: %s", hipGetErrorString(e));
-        wg_per_cu = nb < 1 ? 1 : nb;
-    }
+    constexpr auto kern = stack_tail_kernel<C, H, W, MT, NW, NSPLIT, BACKWARD>;
+    int nb = 0;
+    if (int rc = prepare_kernel<kern>("stack_tail", S::LDS_BYTES, S::WAVES * 64, &nb)) return rc;
+    const int wg_per_cu = nb < 1 ? 1 : nb;
     int grid = 256 * wg_per_cu;
     if (grid > args.n_images) grid = args.n_images;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(S::WAVES * 64), S::LDS_BYTES, st, args);
@@ -506,14 +499,8 @@ template <int C, int H, int W, int TR, bool BACKWARD>
 int launch_stack_shift(const StackTailArgs &args, hipStream_t st)
 {
     using S = ShiftCfg<C, H, W, TR>;
-    auto kern = stack_shift_kernel<C, H, W, TR, BACKWARD>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)S::LDS_BYTES);
-        if (e != hipSuccess) return fail(PPO_E_HIP, "stack_shift: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr_set = true;
-    }
+    constexpr auto kern = stack_shift_kernel<C, H, W, TR, BACKWARD>;
+    if (int rc = prepare_kernel<kern>("stack_shift", S::LDS_BYTES)) return rc;
     int grid = 256;  // one workgroup per CU (150 KB of LDS each)
     if (grid > args.n_images) grid = args.n_images;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(S::NW * 64), S::LDS_BYTES, st, args);
@@ -914,14 +901,8 @@ int launch_stack_full_bwd(const StackFullBwdArgs &args, hipStream_t st)
 {
     using SI = StackCfg<C, HI, WI, MTI, NW, NSPLIT>;
     constexpr size_t kLds = 2 * (size_t)SI::LDS_MAP * 4;
-    auto kern = stack_full_bwd_kernel<C, HI, WI, MTI, HO, WO, MTO, NW, NSPLIT>;
-    static bool ready = false;
-    if (!ready) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)kLds);
-        if (e != hipSuccess) return fail(PPO_E_HIP, "stack_full_bwd: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        ready = true;
-    }
+    constexpr auto kern = stack_full_bwd_kernel<C, HI, WI, MTI, HO, WO, MTO, NW, NSPLIT>;
+    if (int rc = prepare_kernel<kern>("stack_full_bwd", kLds)) return rc;
     const int grid = args.n_images < 256 ? args.n_images : 256;  // one workgroup per CU (LDS)
     hipLaunchKernelGGL(kern, dim3(grid), dim3(SI::WAVES * 64), kLds, st, args);
     return check_launch("stack_full_bwd_kernel");
@@ -932,14 +913,8 @@ int launch_stack_full(const StackFullArgs &args, hipStream_t st)
 {
     using SI = StackCfg<C, HI, WI, MTI, NW, NSPLIT>;
     constexpr size_t kLds = 2 * (size_t)SI::LDS_MAP * 4;
-    auto kern = stack_full_kernel<C, HI, WI, MTI, HO, WO, MTO, NW, NSPLIT>;
-    static bool ready = false;
-    if (!ready) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)kLds);
-        if (e != hipSuccess) return fail(PPO_E_HIP, "stack_full: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        ready = true;
-    }
+    constexpr auto kern = stack_full_kernel<C, HI, WI, MTI, HO, WO, MTO, NW, NSPLIT>;
+    if (int rc = prepare_kernel<kern>("stack_full", kLds)) return rc;
     const int grid = args.n_images < 256 ? args.n_images : 256;  // one workgroup per CU (LDS)
     hipLaunchKernelGGL(kern, dim3(grid), dim3(SI::WAVES * 64), kLds, st, args);
     return check_launch("stack_full_kernel");
@@ -1116,14 +1091,8 @@ int launch_chain_split(const ChainSplitArgs &args, hipStream_t st)
 {
     using SI = StackCfg<C, HI, WI, 7, 4, 2>;
     constexpr size_t kLds = 2 * (size_t)SI::LDS_MAP * 4;
-    auto kern = stack_chain_split_kernel<C, HI, WI, HO, WO>;
-    static bool ready = false;
-    if (!ready) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)kLds);
-        if (e != hipSuccess) return fail(PPO_E_HIP, "stack_chain_split: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        ready = true;
-    }
+    constexpr auto kern = stack_chain_split_kernel<C, HI, WI, HO, WO>;
+    if (int rc = prepare_kernel<kern>("stack_chain_split", kLds)) return rc;
     int groups = (args.n_images + 7) / 8;       // 8 pairs = 16 workgroups per group: b and b ^ 8
     if (groups > 16) groups = 16;               // at most one workgroup per CU; more images: pairs walk them
     hipLaunchKernelGGL(kern, dim3(16 * groups), dim3(kSplitWaves * 64), kLds, st, args);

@@ -508,7 +508,7 @@ int launch_column(const ColumnLds &L, hipStream_t st, const float *rewards, cons
                   const int32_t *nd_of_n, const MainRec *mrec, const LaneRec *lrec, const TailRec *trec,
                   const uint8_t *k_zero, float *out, ColumnArgs args)
 {
-    auto kern = tvf_column_kernel<MAXR>;
+    constexpr auto kern = tvf_column_kernel<MAXR>;
     // timing aid (tools/tvf_phases.sh, a -DPPO_TUNE_TIMING_AIDS build): bit 0 skips the walk, 1 the terms, 2 the stores -
     // results are then garbage; the shipped library has no such switch
 #ifdef PPO_TUNE_TIMING_AIDS
@@ -516,13 +516,7 @@ int launch_column(const ColumnLds &L, hipStream_t st, const float *rewards, cons
 #else
     constexpr int skip = 0;
 #endif
-    static bool attr_set = false;
-    if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)kLdsLimit);
-        if (e != hipSuccess) return fail(PPO_E_HIP, "tvf_column: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        attr_set = true;
-    }
+    if (int rc = prepare_kernel<kern>("tvf_column", kLdsLimit)) return rc;
     args.T = L.T;
     args.PAD = L.PAD;
     args.rw_off = (int)L.rw_off;

@@ -325,23 +325,20 @@ template <int CIN, int COUT, int H, int W, int TR, int NS = 2>
 int launch_split_wgrad(const SplitWgradBatch &b, int count, int n_images, size_t workspace_bytes, int *n_slabs, hipStream_t st)
 {
     using C = SplitWgradCfg<CIN, COUT, H, W, TR, NS>;
-    auto kern = conv3x3_wgrad_bf16x3_kernel<CIN, COUT, H, W, TR, NS>;
-    static int per_cu = 0;
-    if (!per_cu) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)C::LDS_BYTES);
-        if (e != hipSuccess) return fail(PPO_E_HIP, "conv3x3_wgrad_bf16x3: hipFuncSetAttribute: %s", hipGetErrorString(e));
-        int occ = 0;
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, reinterpret_cast<const void *>(kern), kSplitWaves * 64, C::LDS_BYTES);
-        if (e != hipSuccess || occ < 1) return fail(PPO_E_HIP, "conv3x3_wgrad_bf16x3: occupancy query: %s", hipGetErrorString(e));
-        per_cu = occ > 4 ? 4 : occ;
-        if (getenv("PPO_AMD_DEBUG_OCCUPANCY")) {
-            hipFuncAttributes fa{};
-            (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(kern));
-            fprintf(stderr, "conv3x3_wgrad_bf16x3<%d,%d,%d,%d,%d>: occupancy query %d, LDS %d B, %d regs, static LDS %zu\n", CIN, COUT, H, W, TR,
-                    occ, (int)C::LDS_BYTES, fa.numRegs, fa.sharedSizeBytes);
-        }
-    }
+    constexpr auto kern = conv3x3_wgrad_bf16x3_kernel<CIN, COUT, H, W, TR, NS>;
+    int occ = 0;
+    if (int rc = prepare_kernel<kern>("conv3x3_wgrad_bf16x3", C::LDS_BYTES, kSplitWaves * 64, &occ)) return rc;
+    if (occ < 1) return fail(PPO_E_HIP, "conv3x3_wgrad_bf16x3: occupancy query: %s", hipGetErrorString(hipSuccess));
+    const int per_cu = occ > 4 ? 4 : occ;
+    static const bool reported = [&] {  // once per instantiation
+        if (!getenv("PPO_AMD_DEBUG_OCCUPANCY")) return false;
+        hipFuncAttributes fa{};
+        (void)hipFuncGetAttributes(&fa, reinterpret_cast<const void *>(kern));
+        fprintf(stderr, "conv3x3_wgrad_bf16x3<%d,%d,%d,%d,%d>: occupancy query %d, LDS %d B, %d regs, static LDS %zu\n", CIN, COUT, H, W, TR,
+                occ, (int)C::LDS_BYTES, fa.numRegs, fa.sharedSizeBytes);
+        return true;
+    }();
+    (void)reported;
     // one resident wave of workgroups over all problems of the launch; every workgroup writes one slab
     const int n_items = n_images * C::NB;
     int grid = (256 * per_cu) / count;

@@ -337,3 +337,64 @@ def test_residual_block_in_one_launch_is_the_two_convolutions_bitwise(hw, n):
     # no kernel for other shapes: an error, not a silent wrong answer
     rc = lib.ppo_conv3x3_block_forward_packed_f32(_p(x), _p(p0), _p(b0), _p(p1), _p(b1), _p(got), n, c, hw, hw + 1, st)
     assert rc != 0
+
+
+def test_packed_and_indexed_choice_of_one_call_does_not_reach_the_next():
+    """Raw or packed weights and the image index are arguments of one call.  On one stream and thread: the raw-weight,
+    unindexed entry point (R0), the packed + indexed one (Ri), the first again (R1), then packed without an index on the
+    gathered rows (Rp): R1 has R0's bits and Rp has Ri's.  (That packed and indexed results equal the plain ones is
+    test_packed_weights_give_the_raw_weight_results_bitwise and the special-cases test above.)  The same for the first
+    layer's weight gradient with and without the index."""
+    import ctypes
+    lib = _lib.load()
+    dev = torch.device("cuda")
+    st = _lib.current_stream()
+    g = torch.Generator(device=dev).manual_seed(64)
+    cin, cout, hw, n = 3, 16, 64, 2
+    ho = hw // 2
+    x = torch.randint(0, 256, (4, cin, hw, hw), generator=g, device=dev, dtype=torch.uint8)
+    idx = torch.tensor([2, 0], device=dev, dtype=torch.int32)
+    xg = x[idx.long()].contiguous()
+    w = torch.randn(cout, cin, 3, 3, generator=g, device=dev) * 0.2
+    b = torch.randn(cout, generator=g, device=dev)
+    pf = torch.zeros((lib.ppo_conv3x3_packed_floats(cin, cout, 0),), device=dev)
+    jobs = (_lib.PackJob * 1)(_lib.PackJob(_p(w), _p(pf), cin, cout, 0))
+    _lib.check(lib.ppo_conv3x3_pack_weights_f32(ctypes.addressof(jobs), 1, st), "pack")
+
+    def pool(fn, *head):  # head: the arguments before the bias
+        out = torch.full((n, cout, ho, ho), float("nan"), device=dev)
+        amx = torch.full((n, cout, ho, ho), 255, device=dev, dtype=torch.uint8)
+        _lib.check(getattr(lib, fn)(*head, _p(b), _p(out), _p(amx), n, cin, cout, hw, hw, st), fn)
+        return out, amx
+
+    r0 = pool("ppo_conv3x3_pool_forward_f32", _p(xg), _lib.PPO_IN_U8, _p(w))
+    ri = pool("ppo_conv3x3_pool_forward_packed_indexed_f32", _p(x), _p(idx), _lib.PPO_IN_U8, _p(pf))
+    r1 = pool("ppo_conv3x3_pool_forward_f32", _p(xg), _lib.PPO_IN_U8, _p(w))
+    rp = pool("ppo_conv3x3_pool_forward_packed_f32", _p(xg), _lib.PPO_IN_U8, _p(pf))
+    torch.cuda.synchronize()
+    assert torch.equal(r1[0], r0[0]) and torch.equal(r1[1], r0[1])
+    assert torch.equal(rp[0], ri[0]) and torch.equal(rp[1], ri[1])
+
+    gp = torch.randn(n, cout, ho, ho, generator=g, device=dev)  # the pooled gradient
+    amx = r0[1]
+    ws_bytes = lib.ppo_conv3x3_wgrad_workspace_bytes(cin, cout)
+
+    def wgrad(fn, *head):  # head: the arguments before in_mode
+        ws = torch.empty(ws_bytes // 4, device=dev)
+        dw = torch.full((cout, cin, 3, 3), float("nan"), device=dev)
+        db = torch.full((cout,), float("nan"), device=dev)
+        n_slabs = ctypes.c_int(0)
+        _lib.check(getattr(lib, fn)(*head, _lib.PPO_IN_U8, _p(gp), _p(amx), _p(ws), ws_bytes, n, cin, cout, hw, hw,
+                                    ctypes.addressof(n_slabs), st), fn)
+        table = (_lib.WgradJob * 1)(_lib.WgradJob(_p(ws), _p(dw), _p(db), n_slabs.value, cin, cout, 0))
+        _lib.check(lib.ppo_conv3x3_wgrad_reduce_f32(ctypes.addressof(table), 1, st), "reduce")
+        torch.cuda.synchronize()
+        return dw, db
+
+    g0 = wgrad("ppo_conv3x3_backward_weight_slabs_pooled_f32", _p(xg))
+    gi = wgrad("ppo_conv3x3_backward_weight_slabs_pooled_indexed_f32", _p(x), _p(idx))
+    g1 = wgrad("ppo_conv3x3_backward_weight_slabs_pooled_f32", _p(xg))
+    gn = wgrad("ppo_conv3x3_backward_weight_slabs_pooled_indexed_f32", _p(xg), None)
+    assert torch.isfinite(g0[0]).all() and float(g0[0].abs().max()) > 0
+    assert torch.equal(g1[0], g0[0]) and torch.equal(g1[1], g0[1])
+    assert torch.equal(gn[0], gi[0]) and torch.equal(gn[1], gi[1])
