@@ -49,11 +49,15 @@ struct StackTailArgs {
 // NW pixel-tile waves x NSPLIT channel-tile groups: wave = ng * NW + pw computes MT pixel tiles x NT / NSPLIT channel
 // tiles.  NSPLIT = 2 puts two waves on every SIMD of the CU the image owns, so one wave's operand reads, med3s and
 // epilogue issue under the other's MFMAs.
-template <int C, int H, int W, int MT, int NW, int NSPLIT>
+// PITCH = floats from row to row.  W: the flat band layout of conv3x3.hip, edge taps clamped by the K loop's med3.
+// W + 1 (the chained backward): one zero float behind every row, the right pad of row y and the left pad of row y + 1,
+// and no VALU in the K loop (resident_conv).
+template <int C, int H, int W, int MT, int NW, int NSPLIT, int PITCH_ = W>
 struct StackCfg {
     static constexpr int ROWS = H + 2;
     static constexpr int G = 4;
-    static constexpr int PLANE_RAW = ROWS * W + 2 * G;
+    static constexpr int PITCH = PITCH_;
+    static constexpr int PLANE_RAW = ROWS * PITCH + 2 * G;
     static constexpr int PLANE = PLANE_RAW + ((16 - PLANE_RAW % 32) + 32) % 32;  // = 16 (mod 32)
     static constexpr int NT = C / 16;            // channel tiles of the layer
     static constexpr int NTL = NT / NSPLIT;      // ... of one wave
@@ -273,7 +277,8 @@ int launch_stack_tail(const StackTailArgs &args, hipStream_t st)
 // layer boundary (it still holds the last row of the previous map).  The skip connection of the odd layers (the block
 // input: p or q0; backward: g or g1) is re-read from HBM — the kernel's own input or what layer 1 wrote two layers
 // earlier — as 16-byte loads in the transposed epilogue of conv3x3.hip's WIDE path, which this kernel shares, as it
-// does the K loop and the arithmetic order: results are bit-identical to the four launches.
+// does the K order and the arithmetic order (the K loop itself carries no med3 here: padded rows, see the kernel):
+// results are bit-identical to the four launches.
 //
 // What it removes from the four launches: three kernel boundaries with their weight prologues and ragged tails, and
 // the HBM -> LDS band staging (with its halo re-reads and the DMA waits at every item barrier) of layers 2-4.
@@ -284,8 +289,10 @@ struct ShiftCfg {
     static constexpr int GW = 8;                 // waves of a group = pixel-tile groups of a band (two per SIMD: a lone
                                                  // wave leaves the MFMA pipe idle while it prepares its next operands)
     static constexpr int G = 4;
+    static constexpr int PITCH = W + 2;          // floats from row to row: two zero pad slots follow every row (the right
+                                                 // pad of row y and the left pad of row y + 1); even, for the 8-byte stores
     static constexpr int ROWS = H + 6;           // 4 rows of head-room + a halo row above and below
-    static constexpr int PLANE_RAW = ROWS * W + 2 * G;
+    static constexpr int PLANE_RAW = ROWS * PITCH + 2 * G;
     static constexpr int PLANE = PLANE_RAW + ((16 - PLANE_RAW % 32) + 32) % 32;  // = 16 (mod 32)
     static constexpr int KS = 9 * (C / 4);
     static constexpr int NBANDS = (H + TR - 1) / TR;
@@ -308,51 +315,90 @@ struct ShiftCfg {
 // reads (>= y0 + TR - 1), and were last read two half-steps (two barriers) ago by the K loop of the band before, so one
 // barrier per half-step is all the ordering there is.  With every wave in the same phase (the first form of this
 // kernel) the MFMA pipe idled through every barrier and epilogue: 9.1 k cycles per band for 4.6 k of MFMA work.
+//
+// The K loop is ds_read_b32 + MFMA and nothing else: on gfx950 a VALU instruction takes the MFMA's datapath
+// (profiles/r04p_mfma_valu_mix.md), and with one channel tile per wave every B operand feeds exactly one MFMA, so the
+// med3 per operand that conv3x3.hip's loop carries (ReLU on read, edge taps clamped to zero) cost 4.9 of ~37 cycles
+// per K step.  Here the resident map holds exactly what the MFMA is to take:
+//  - rows are PITCH = W + 2 floats apart and the two floats behind each row are zero: the right pad of row y and the
+//    left pad of row y + 1, so a kx = 0 / kx = 2 tap at the map's edge reads a stored 0 where med3 clamped to 0.
+//    INVARIANT: the pad slots (and the guards) are zeroed once, when the kernel starts, and nobody writes them after
+//    that - staging, the epilogues' pair stores and the row clears address columns 0 .. W - 1 only;
+//  - forward: the map holds relu1(value).  The first map is ReLU'd as it is staged (through registers), every later one
+//    by the epilogue that writes it (the HBM copy `save` stays raw, and the skip operand comes from HBM).  One relu1 per
+//    element where there were nine, one per tap that read it;
+//  - backward: the map holds the raw gradient, only the pitch differs.
+// Bit identity with the med3 loop: every MFMA receives the operand value it received - relu1 is the same med3 applied to
+// the same number, the clamped edge taps were 0 and read 0 - except possibly the SIGN of a zero (med3(-0, 0, inf) and a
+// clamp of a negative edge value may give either zero; a pad is +0).  A zero of either sign contributes a product
+// of +-0, and an accumulator that starts at +0 and takes sums of such products can never be -0 ((+0) + (+-0) = +0,
+// x + (-x) = +0), so the accumulators are the same bits.  Non-finite inputs: +-inf behave as before (relu1 keeps
+// +inf and zeroes -inf; a clamped edge tap is 0 either way).  NaN, forward: med3 returns min3 of its operands when one
+// is NaN and min ignores a NaN, so relu1(NaN) = 0 at staging / in the epilogue exactly as it was in the loop - no
+// change.  NaN, backward: the old loop passed a NaN unchanged on the three kx = 1 taps but turned it into -inf
+// (med3(NaN, -inf, inf)) on the six kx != 1 taps; now all nine taps pass it unchanged, so a NaN in the incoming
+// gradient reaches every neighbour as NaN where six of them used to see -inf.  Both are garbage from garbage.
+//
+// Bank conflicts: a 16-pixel tile that crosses a row end (W = 42: about a third of them; W = 32: none) now spans 18
+// addresses, so two of its banks meet the tile of the other channel group in the ds_read_b32's 32-lane half
+// (PLANE = 16 mod 32): a 2-way conflict on that read.  No PLANE residue avoids it (profiles/stack_pitch.md).
 template <int C, int H, int W, int TR, bool BACKWARD>
 __global__ __launch_bounds__(1024) void stack_shift_kernel(StackTailArgs a)
 {
     using S = ShiftCfg<C, H, W, TR>;
-    constexpr int KS = S::KS, PLANE = S::PLANE, G = S::G, MT = S::MT, NW = S::NW;
+    constexpr int KS = S::KS, PLANE = S::PLANE, PITCH = S::PITCH, G = S::G, MT = S::MT, NW = S::NW;
     extern __shared__ __align__(16) float smem[];
     const int tid = threadIdx.x, lane = tid & 63, l15 = lane & 15, g = lane >> 4, wave = tid >> 6;
     const int grp = __builtin_amdgcn_readfirstlane(wave / S::GW), wv = wave % S::GW;
     const int ch = lane >> 2, quad = lane & 3;  // transposed epilogue: channel ch, pixels quad*4 .. +3 of a tile
     float *scr = smem + S::LDS_MAP + wv * S::SCR;
 
+    // The pad slots (the two floats behind every row) and the guards are zeroed here, once.  Nothing writes them
+    // afterwards: staging, the epilogues and the row clears all address columns 0 .. W - 1 of a row only.
+    zero_lds<S::LDS_MAP, NW * 64>(smem, tid);
+
     // per-lane constants of this wave's pixel tiles inside a band (identical for every band, layer and image)
-    int lofs[MT], p4[MT];
-    float hi_l[MT], hi_r[MT];
+    int lofs[MT], p4[MT], po[MT][2];
 #pragma unroll
     for (int m = 0; m < MT; ++m) {
         const int p = (wv * MT + m) * 16 + l15;
-        lofs[m] = G + p - 1 + g * PLANE;  // window origin (row above, x - 1) relative to the band's first input row
-        hi_l[m] = (p % W == 0) ? 0.f : INFINITY;
-        hi_r[m] = (p % W == W - 1) ? 0.f : INFINITY;
+        // window origin (row above, x - 1) relative to the band's first input row
+        lofs[m] = G + (p / W) * PITCH + p % W - 1 + g * PLANE;
         p4[m] = (wv * MT + m) * 16 + quad * 4;
+        // the epilogue's quad as two pairs: W is even and p4 a multiple of 4, so each pair lies within one row
+        po[m][0] = (p4[m] / W) * PITCH + p4[m] % W;
+        po[m][1] = ((p4[m] + 2) / W) * PITCH + (p4[m] + 2) % W;
     }
 
     for (int img = blockIdx.x; img < a.n_images; img += gridDim.x) {
         const size_t img_off = (size_t)img * C * H * W;
-        __syncthreads();  // the previous image's last readers are done
+        __syncthreads();  // the previous image's last readers are done (first image: the zeros above are written)
         // head-room + top halo rows (0 .. 4) and the bottom halo row (H + 5) are zero; rows 5 .. H + 4 take the image
         for (int i = tid; i < C * 6 * W; i += NW * 64) {
             const int c = i / (6 * W), r = (i / W) % 6, x = i % W;
-            smem[c * PLANE + G + (r < 5 ? r : H + 5) * W + x] = 0.f;
+            smem[c * PLANE + G + (r < 5 ? r : H + 5) * PITCH + x] = 0.f;
         }
-        for (int i = tid; i < C * 2 * G; i += NW * 64)  // guards in front of and behind the rows
-            smem[(i / (2 * G)) * PLANE + ((i % (2 * G)) < G ? (i % G) : G + S::ROWS * W + (i % G))] = 0.f;
-        {   // X <- in: a channel's H * W floats are one run (flat layout), 16-byte LDS-DMA requests
-            using gptr_t = const __attribute__((address_space(1))) void *;
-            using lptr_t = __attribute__((address_space(3))) void *;
-            constexpr int N4 = H * W / 4, REQ = (N4 + 63) / 64;
+        {   // X <- f(in) through registers (LDS-DMA can neither apply the ReLU nor, with 16-byte requests, skip the pad
+            // slots; backward with one 4-byte-per-lane DMA request per row measured 0.9 us slower than this,
+            // profiles/stack_pitch.md): a wave takes a channel, RP whole rows of 8-byte pairs per request (a pair never straddles a row: W
+            // is even), so every address is one per-lane base + a compile-time offset, and all of a channel's loads are
+            // in flight before the first LDS store
+            constexpr int W2 = W / 2, RP = 64 / W2, NQ = H / RP;
+            static_assert(H % RP == 0, "whole requests");
             const int w0 = __builtin_amdgcn_readfirstlane(wave);
+            const bool live = lane < RP * W2;
+            const int ls = live ? lane : RP * W2 - 1;  // the lanes left over re-read the last pair and store nothing
             for (int c = w0; c < C; c += NW) {
-                const float *g0 = a.in + img_off + (size_t)c * H * W;
-                float *l0 = smem + c * PLANE + G + 5 * W;
+                const float2 *g2 = reinterpret_cast<const float2 *>(a.in + img_off + (size_t)c * H * W) + ls;
+                float *l0 = smem + c * PLANE + G + (5 + ls / W2) * PITCH + (ls % W2) * 2;
+                float2 v[NQ];
 #pragma unroll
-                for (int q = 0; q < REQ; ++q)
-                    if (q * 64 + lane < N4)
-                        __builtin_amdgcn_global_load_lds((gptr_t)(g0 + (q * 64 + lane) * 4), (lptr_t)(l0 + q * 256), 16, 0, 0);
+                for (int q = 0; q < NQ; ++q) v[q] = g2[q * RP * W2];
+#pragma unroll
+                for (int q = 0; q < NQ; ++q) {
+                    const float2 o = BACKWARD ? v[q] : make_float2(relu1(v[q].x), relu1(v[q].y));
+                    if (live) *reinterpret_cast<float2 *>(l0 + q * RP * PITCH) = o;
+                }
             }
         }
 
@@ -394,13 +440,28 @@ __global__ __launch_bounds__(1024) void stack_shift_kernel(StackTailArgs a)
                             if constexpr (BACKWARD) gate4[m] = buffer_f32x4(mask_b, off);
                             res4[m] = buffer_f32x4(res_b, off);
                         }
-                        int base[MT];
+                        // A ds_read's immediate offset is 16 bits of bytes.  Where the last channel steps of the last tap
+                        // lie beyond that (42x42), channel steps 2 and 3 read from a second base register, hidden from the
+                        // compiler: folded back into base + constant it would be split again as one v_add per read, in a
+                        // loop where a VALU instruction costs MFMA time.
+                        constexpr int CS_HI = ((C / 4 - 1) * 4 * PLANE + 2 * PITCH + 2) * 4 > 65535 ? C / 8 : C / 4;
+                        static_assert(((C / 4 - 1 - (CS_HI < C / 4 ? CS_HI : 0)) * 4 * PLANE + 2 * PITCH + 2) * 4 <= 65535 &&
+                                      ((CS_HI - 1) * 4 * PLANE + 2 * PITCH + 2) * 4 <= 65535, "operand offsets fit the instruction");
+                        // Operand reads are volatile so that each stays one ds_read_b32 with its offset in the instruction:
+                        // merged in pairs (ds_read2st64_b32, whose offsets count in units of 64 dwords) every pair needs a
+                        // v_add for the tap offset.
+                        using lds_cvf = const volatile __attribute__((address_space(3))) float;
+                        lds_cvf *vsmem = (lds_cvf *)smem;
+                        int base[MT], base_hi[MT];
 #pragma unroll
                         for (int m = 0; m < MT; ++m) {
-                            base[m] = lofs[m] + (y0 - 1 + in_row) * W;
+                            base[m] = lofs[m] + (y0 - 1 + in_row) * PITCH;
+                            base_hi[m] = base[m] + CS_HI * 4 * PLANE;
+                            if constexpr (CS_HI < C / 4) asm volatile("" : "+v"(base_hi[m]));
                             acc[m] = f32x4{0.f, 0.f, 0.f, 0.f};
                         }
-                        // the block pipeline of conv3x3.hip / stack_tail_kernel
+                        // the block pipeline of conv3x3.hip / stack_tail_kernel in its K order, without that loop's
+                        // per-operand med3: the map holds what the MFMA takes (see the comment above the kernel)
                         constexpr int SB = 2;
                         constexpr int NB = (KS + SB - 1) / SB;
                         float raw[2][SB][MT];
@@ -410,42 +471,26 @@ __global__ __launch_bounds__(1024) void stack_shift_kernel(StackTailArgs a)
                                 const int s = j * SB + u;
                                 if (s < KS) {
                                     const int tap = s / (C / 4), cs = s % (C / 4);
-                                    const int tap_off = (tap / 3) * W + (tap % 3);
+                                    const int tap_off = (tap / 3) * PITCH + (tap % 3);
 #pragma unroll
-                                    for (int m = 0; m < MT; ++m) r[u][m] = smem[base[m] + cs * 4 * PLANE + tap_off];
+                                    for (int m = 0; m < MT; ++m)  // volatile: see vsmem
+                                        r[u][m] = cs < CS_HI ? vsmem[base[m] + cs * 4 * PLANE + tap_off]
+                                                             : vsmem[base_hi[m] + (cs - CS_HI) * 4 * PLANE + tap_off];
                                 }
                             }
                         };
                         load_block(0, raw[0]);
 #pragma unroll
                         for (int j = 0; j < NB; ++j) {
-                            float bv[SB][MT];
-#pragma unroll
-                            for (int u = 0; u < SB; ++u) {
-                                const int s = j * SB + u;
-                                if (s < KS) {
-                                    const int kx = (s / (C / 4)) % 3;
-#pragma unroll
-                                    for (int m = 0; m < MT; ++m) {
-                                        float x = raw[j & 1][u][m];
-                                        if (kx != 1) {
-                                            const float hi = kx == 0 ? hi_l[m] : hi_r[m];
-                                            x = __builtin_amdgcn_fmed3f(x, BACKWARD ? -hi : 0.f, hi);
-                                        } else if (!BACKWARD) {
-                                            x = relu1(x);
-                                        }
-                                        bv[u][m] = x;
-                                    }
-                                }
-                            }
                             __builtin_amdgcn_sched_barrier(0);
                             if (j + 1 < NB) load_block(j + 1, raw[(j + 1) & 1]);
+                            __builtin_amdgcn_sched_barrier(0);  // the next block's reads stay in front of this block's MFMAs
 #pragma unroll
                             for (int u = 0; u < SB; ++u) {
                                 const int s = j * SB + u;
                                 if (s < KS) {
 #pragma unroll
-                                    for (int m = 0; m < MT; ++m) acc[m] = mfma16(wa[s], bv[u][m], acc[m]);
+                                    for (int m = 0; m < MT; ++m) acc[m] = mfma16(wa[s], raw[j & 1][u][m], acc[m]);
                                 }
                             }
                             __builtin_amdgcn_sched_barrier(0);
@@ -454,7 +499,7 @@ __global__ __launch_bounds__(1024) void stack_shift_kernel(StackTailArgs a)
                         // last half-step, no band left for this group: the row below the new map still holds the old
                         // map's last row (read for the last time one barrier ago): it is the next layer's bottom halo
                         for (int i = tid % (S::GW * 64); i < C * W; i += S::GW * 64)
-                            smem[(i / W) * PLANE + G + (H + in_row - 1) * W + i % W] = 0.f;
+                            smem[(i / W) * PLANE + G + (H + in_row - 1) * PITCH + i % W] = 0.f;
                     }
                 } else if (hs >= 1) {
                     // ---------------- epilogue half-step of band hs - 1
@@ -466,7 +511,7 @@ __global__ __launch_bounds__(1024) void stack_shift_kernel(StackTailArgs a)
 #pragma unroll
                         for (int r = 0; r < 4; ++r) scr[(m * 16 + g * 4 + r) * kScrPitchS + l15] = acc[m][r];
                     __builtin_amdgcn_wave_barrier();
-                    float *out_row = smem + ch * PLANE + G + (y0 + in_row - 1) * W;  // output row y sits where input row y - 1 sat
+                    float *out_row = smem + ch * PLANE + G + (y0 + in_row - 1) * PITCH;  // output row y sits where input row y - 1 sat
 #pragma unroll
                     for (int m = 0; m < MT; ++m) {
                         if (p4[m] >= S::NPIX) continue;
@@ -481,9 +526,12 @@ __global__ __launch_bounds__(1024) void stack_shift_kernel(StackTailArgs a)
                             if constexpr (BACKWARD) val = gv[e] > 0.f ? val : 0.f;
                             v[e] = val + rv[e];
                         }
-                        if (layer < 3) {  // the next layer's input (8-byte stores: rows are W = 2 (mod 4) floats apart)
-                            *reinterpret_cast<float2 *>(out_row + p4[m]) = make_float2(v[0], v[1]);
-                            *reinterpret_cast<float2 *>(out_row + p4[m] + 2) = make_float2(v[2], v[3]);
+                        if (layer < 3) {  // the next layer's input, as its K loop takes it: forward relu(v), backward v
+                            float t[4];
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) t[e] = BACKWARD ? v[e] : relu1(v[e]);
+                            *reinterpret_cast<float2 *>(out_row + po[m][0]) = make_float2(t[0], t[1]);
+                            *reinterpret_cast<float2 *>(out_row + po[m][1]) = make_float2(t[2], t[3]);
                         }
                         if (save) *reinterpret_cast<float4 *>(save + chan_off + p4[m]) = make_float4(v[0], v[1], v[2], v[3]);
                     }
@@ -501,7 +549,7 @@ int launch_stack_shift(const StackTailArgs &args, hipStream_t st)
     using S = ShiftCfg<C, H, W, TR>;
     constexpr auto kern = stack_shift_kernel<C, H, W, TR, BACKWARD>;
     if (int rc = prepare_kernel<kern>("stack_shift", S::LDS_BYTES)) return rc;
-    int grid = 256;  // one workgroup per CU (150 KB of LDS each)
+    int grid = 256;  // one workgroup per CU (153 KB of LDS each at 42x42)
     if (grid > args.n_images) grid = args.n_images;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(S::NW * 64), S::LDS_BYTES, st, args);
     return check_launch("stack_shift_kernel");
@@ -535,7 +583,7 @@ struct LaneMap {  // where this lane's pixel tiles live in a resident map
     };
 };
 
-template <int H, int W, int PLANE, int G, int MT>
+template <int H, int W, int PLANE, int G, int MT, int PITCH = W>
 __device__ __forceinline__ void lane_map_init(LaneMap::T<MT> &lm, int pixel_wave, int l15, int g)
 {
 #pragma unroll
@@ -543,9 +591,14 @@ __device__ __forceinline__ void lane_map_init(LaneMap::T<MT> &lm, int pixel_wave
         const int p = (pixel_wave * MT + m) * 16 + l15;
         lm.pix[m] = p;
         const int pc = p < H * W ? p : 0;
-        lm.lofs[m] = G + pc - 1 + g * PLANE;
-        lm.hi_l[m] = (pc % W == 0) ? 0.f : INFINITY;
-        lm.hi_r[m] = (pc % W == W - 1) ? 0.f : INFINITY;
+        if constexpr (PITCH == W) {
+            lm.lofs[m] = G + pc - 1 + g * PLANE;
+            lm.hi_l[m] = (pc % W == 0) ? 0.f : INFINITY;
+            lm.hi_r[m] = (pc % W == W - 1) ? 0.f : INFINITY;
+        } else {  // padded rows: no clamps (never read)
+            lm.lofs[m] = G + (pc / W) * PITCH + pc % W - 1 + g * PLANE;
+            lm.hi_l[m] = lm.hi_r[m] = 0.f;
+        }
     }
 }
 
@@ -553,14 +606,21 @@ __device__ __forceinline__ void lane_map_init(LaneMap::T<MT> &lm, int pixel_wave
 // smem + src_off / dst_off; `save` (nullable) receives the HBM copy of this image's result.
 // GATED (backward-data): the result is zeroed where `mask` (this image's forward pre-activation map) is <= 0, before
 // the residual add; bias is then null.
-template <int C, int H, int W, int MT, int NTOT, int NT, bool RELU_IN, bool GATED = false>
+// PITCH = W + 1 (StackCfg; identity input only): both maps have a zero float behind every row - zeroed by the kernel,
+// and written by nobody: this function's epilogue, like every other writer, addresses columns 0 .. W - 1 - so an edge
+// tap reads the 0 the med3 clamped it to and the K loop is ds_read_b32 + MFMA.  Same operand values into the same MFMAs
+// in the same order: the same bits (a zero of the other sign cannot change an accumulator that starts at +0), except that a
+// NaN in the source now reaches all nine taps as NaN, where med3(NaN, -inf, inf) = -inf on the six kx != 1 taps before.
+template <int C, int H, int W, int MT, int NTOT, int NT, bool RELU_IN, bool GATED = false, int PITCH = W>
 __device__ __forceinline__ void resident_conv(float *smem, int src_off, int dst_off, bool residual, const float *wpk,
                                               const float *bias, float *save, const LaneMap::T<MT> &lm, int n0, int lane,
                                               const float *mask = nullptr)
 {
-    constexpr int ROWS = H + 2, G = 4, PLANE_RAW = ROWS * W + 2 * G;
+    constexpr int ROWS = H + 2, G = 4, PLANE_RAW = ROWS * PITCH + 2 * G;
     constexpr int PLANE = PLANE_RAW + ((16 - PLANE_RAW % 32) + 32) % 32;
     constexpr int KS = 9 * (C / 4);
+    constexpr bool PADDED = PITCH != W;
+    static_assert(!PADDED || (PITCH == W + 1 && !RELU_IN), "padded maps hold what the MFMA takes: identity input only");
     const int g = lane >> 4;
     float wa[NT][KS];
     const float4 *pw = reinterpret_cast<const float4 *>(wpk);
@@ -602,7 +662,12 @@ __device__ __forceinline__ void resident_conv(float *smem, int src_off, int dst_
     __syncthreads();  // the source map is complete
     int base[MT];
 #pragma unroll
-    for (int m = 0; m < MT; ++m) base[m] = lm.lofs[m] + src_off;
+    for (int m = 0; m < MT; ++m) {
+        base[m] = lm.lofs[m] + src_off;
+        // (hidden from the compiler: it would otherwise form the KS * MT operand addresses of a layer outside the layer
+        // loop and keep them in registers it does not have, instead of one base and an offset in each instruction)
+        if constexpr (PADDED) asm volatile("" : "+v"(base[m]));
+    }
     f32x4 acc[NT][MT];
 #pragma unroll
     for (int n = 0; n < NT; ++n)
@@ -616,12 +681,23 @@ __device__ __forceinline__ void resident_conv(float *smem, int src_off, int dst_
             const int s = j * SB + u;
             if (s < KS) {
                 const int tap = s / (C / 4), cs = s % (C / 4);
-                const int tap_off = (tap / 3) * W + (tap % 3);
+                const int tap_off = (tap / 3) * PITCH + (tap % 3);
 #pragma unroll
-                for (int m = 0; m < MT; ++m) r[u][m] = smem[base[m] + cs * 4 * PLANE + tap_off];
+                for (int m = 0; m < MT; ++m) {
+                    if constexpr (PADDED) {
+                        // volatile: each read stays one ds_read_b32 with its offset in the instruction.  Merged in pairs
+                        // (ds_read2st64_b32 counts its offsets in units of 64 dwords) every pair takes a v_add for the
+                        // tap offset - VALU work in a loop that was just cleared of it.
+                        using lds_cvf = const volatile __attribute__((address_space(3))) float;
+                        r[u][m] = ((lds_cvf *)smem)[base[m] + cs * 4 * PLANE + tap_off];
+                    } else {
+                        r[u][m] = smem[base[m] + cs * 4 * PLANE + tap_off];
+                    }
+                }
             }
         }
     };
+    static_assert(!PADDED || ((C / 4 - 1) * 4 * PLANE + 2 * PITCH + 2) * 4 <= 65535, "operand offsets fit the instruction");
     load_block(0, raw[0]);
     static_for<0, NB>([&](auto jc) {
         constexpr int j = decltype(jc)::value;
@@ -634,7 +710,8 @@ __device__ __forceinline__ void resident_conv(float *smem, int src_off, int dst_
 #pragma unroll
                 for (int m = 0; m < MT; ++m) {
                     float x = raw[j & 1][u][m];
-                    if (kx != 1) {
+                    if constexpr (PADDED) {
+                    } else if (kx != 1) {
                         const float hi = kx == 0 ? lm.hi_l[m] : lm.hi_r[m];
                         x = __builtin_amdgcn_fmed3f(x, RELU_IN ? 0.f : -hi, hi);
                     } else if (RELU_IN) {
@@ -646,6 +723,7 @@ __device__ __forceinline__ void resident_conv(float *smem, int src_off, int dst_
         }
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (j + 1 < NB) load_block(j + 1, raw[(j + 1) & 1]);
+        if constexpr (PADDED) __builtin_amdgcn_sched_barrier(0);  // the next block's reads stay in front of this block's MFMAs
         if constexpr (j == GATE_AT) load_gate();
 #pragma unroll
         for (int u = 0; u < SB; ++u) {
@@ -667,7 +745,9 @@ __device__ __forceinline__ void resident_conv(float *smem, int src_off, int dst_
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int co = (n0 + n) * 16 + g * 4 + r;
-                    const int lo = dst_off + co * PLANE + G + W + lm.pix[m];
+                    // (padded: the pixel's place in a plane is the window origin lofs one row down, one column right)
+                    const int lo = PADDED ? dst_off + co * PLANE + (lm.lofs[m] - g * PLANE) + PITCH + 1
+                                          : dst_off + co * PLANE + G + W + lm.pix[m];
                     float val = acc[n][m][r] + bias_r[n][r];
                     if constexpr (GATED) val = gate[m][n][r] > 0.f ? val : 0.f;
                     if (residual) val = val + smem[lo];
@@ -799,8 +879,10 @@ struct StackFullBwdArgs {
 template <int C, int HI, int WI, int MTI, int HO, int WO, int MTO, int NW, int NSPLIT>
 __global__ __launch_bounds__(NW * NSPLIT * 64) void stack_full_bwd_kernel(StackFullBwdArgs a)
 {
-    using SI = StackCfg<C, HI, WI, MTI, NW, NSPLIT>;
-    using SO = StackCfg<C, HO, WO, MTO, NW, NSPLIT>;
+    // every convolution here takes its input as it is (no ReLU on read), so all four maps are padded: a zero float
+    // behind each row, no VALU in the K loops (StackCfg, resident_conv)
+    using SI = StackCfg<C, HI, WI, MTI, NW, NSPLIT, WI + 1>;
+    using SO = StackCfg<C, HO, WO, MTO, NW, NSPLIT, WO + 1>;
     static_assert(2 * SO::LDS_MAP <= SI::LDS_MAP, "the small maps live inside the first big map's LDS");
     static_assert(C * HO * WO <= SO::LDS_MAP * 4, "the argmax bytes of an image fit the second small map");
     constexpr int NT = SI::NTL, WAVES = SI::WAVES, THREADS = WAVES * 64;
@@ -811,17 +893,27 @@ __global__ __launch_bounds__(NW * NSPLIT * 64) void stack_full_bwd_kernel(StackF
 
     LaneMap::T<MTI> lmi;
     LaneMap::T<MTO> lmo;
-    lane_map_init<HI, WI, SI::PLANE, SI::G, MTI>(lmi, pixel_wave, l15, g);
-    lane_map_init<HO, WO, SO::PLANE, SO::G, MTO>(lmo, pixel_wave, l15, g);
+    lane_map_init<HI, WI, SI::PLANE, SI::G, MTI, SI::PITCH>(lmi, pixel_wave, l15, g);
+    lane_map_init<HO, WO, SO::PLANE, SO::G, MTO, SO::PITCH>(lmo, pixel_wave, l15, g);
 
-    zero_lds<SI::LDS_MAP, THREADS>(smem + B_OFF, tid);  // dc's halo rows and guards: only its interior is ever written
+    zero_lds<SI::LDS_MAP, THREADS>(smem + B_OFF, tid);  // dc's halo rows, pads and guards: only its interior is ever written
 
     for (int img = blockIdx.x; img < a.n_images; img += gridDim.x) {
         __syncthreads();  // the previous image's transposed first convolution has read B and written A
-        zero_lds<2 * SO::LDS_MAP, THREADS>(smem + X_OFF, tid);  // X, Y: halo rows and guards (A's interior overlaps them)
+        zero_lds<2 * SO::LDS_MAP, THREADS>(smem + X_OFF, tid);  // X, Y: halo rows, pads and guards (A's interior overlaps them)
         __syncthreads();
-        stage_band_chunk_dma<C, HO, WO, SO::ROWS, SO::PLANE, SO::G, WAVES>(a.g, img, 0, smem + X_OFF, tid);
         const size_t small_img = (size_t)img * C * HO * WO, big_img = (size_t)img * C * HI * WI;
+        // X <- g, through registers into the padded rows (15 KB): a thread takes a (channel, row), so its addresses are two
+        // bases + compile-time offsets, and all its loads are in flight before its first LDS store
+        for (int row = tid; row < C * HO; row += THREADS) {
+            const float *gr = a.g + small_img + row * WO;
+            float *lr = smem + X_OFF + (row / HO) * SO::PLANE + SO::G + (1 + row % HO) * SO::PITCH;
+            float gv[WO];
+#pragma unroll
+            for (int x = 0; x < WO; ++x) gv[x] = gr[x];
+#pragma unroll
+            for (int x = 0; x < WO; ++x) lr[x] = gv[x];
+        }
         // this image's argmax bytes are requested now and parked in Y when the blocks are through with it: the gather
         // below reads each of them four times, and from HBM every round of it waited out a memory latency
         constexpr int AM_WORDS = C * HO * WO / 4, AM_PER = (AM_WORDS + THREADS - 1) / THREADS;
@@ -835,7 +927,7 @@ __global__ __launch_bounds__(NW * NSPLIT * 64) void stack_full_bwd_kernel(StackF
 #pragma unroll 1
         for (int layer = 0; layer < 4; ++layer) {
             const int odd = layer & 1;
-            resident_conv<C, HO, WO, MTO, SO::NT, NT, false, true>(smem, odd ? Y_OFF : X_OFF, odd ? X_OFF : Y_OFF, odd != 0,
+            resident_conv<C, HO, WO, MTO, SO::NT, NT, false, true, SO::PITCH>(smem, odd ? Y_OFF : X_OFF, odd ? X_OFF : Y_OFF, odd != 0,
                                                                    a.w[layer], nullptr, a.save[layer] + small_img, lmo, n0,
                                                                    lane, a.mask[layer] + small_img);
         }
@@ -858,29 +950,29 @@ __global__ __launch_bounds__(NW * NSPLIT * 64) void stack_full_bwd_kernel(StackF
                 const bool odd_x = ix & 1;
                 const bool has_ox1 = odd_x && (k + 1 < WO);
                 const int kx0 = odd_x ? 2 : 1;  // this pixel's tap column inside window ox = k
-                const float *gx = smem + X_OFF + co * SO::PLANE + SO::G + WO;
+                const float *gx = smem + X_OFF + co * SO::PLANE + SO::G + SO::PITCH;  // (padded rows; the argmax bytes are flat)
                 const uint8_t *ac = am + co * (HO * WO);
                 float sum = 0.f;
                 {
-                    const int i00 = oy0 * WO + k;
-                    if (ac[i00] == ky0 * 3 + kx0) sum += gx[i00];
-                    if (has_ox1 && ac[i00 + 1] == ky0 * 3 + 0) sum += gx[i00 + 1];
+                    const int i00 = oy0 * WO + k, x00 = oy0 * SO::PITCH + k;
+                    if (ac[i00] == ky0 * 3 + kx0) sum += gx[x00];
+                    if (has_ox1 && ac[i00 + 1] == ky0 * 3 + 0) sum += gx[x00 + 1];
                 }
                 if (has_oy1) {
-                    const int i10 = (oy0 + 1) * WO + k;
-                    if (ac[i10] == kx0) sum += gx[i10];
-                    if (has_ox1 && ac[i10 + 1] == 0) sum += gx[i10 + 1];
+                    const int i10 = (oy0 + 1) * WO + k, x10 = (oy0 + 1) * SO::PITCH + k;
+                    if (ac[i10] == kx0) sum += gx[x10];
+                    if (has_ox1 && ac[i10 + 1] == 0) sum += gx[x10 + 1];
                 }
-                smem[B_OFF + co * SI::PLANE + SI::G + WI + r] = sum;
+                smem[B_OFF + co * SI::PLANE + SI::G + (1 + iy) * SI::PITCH + ix] = sum;
                 a.dc[big_img + e] = sum;
             }
         }
         if (a.has_post) {
             __syncthreads();  // the gather has read X for the last time
-            zero_lds<SI::LDS_MAP, THREADS>(smem + A_OFF, tid);  // A becomes a source below: its halo rows and guards
+            zero_lds<SI::LDS_MAP, THREADS>(smem + A_OFF, tid);  // A becomes a source below: its halo rows, pads and guards
         }
         // ---- first convolution, transposed: B (dc) -> A (overwrites the small maps; its barrier publishes B and A's zeros)
-        resident_conv<C, HI, WI, MTI, SI::NT, NT, false, false>(smem, B_OFF, A_OFF, false, a.w[4], nullptr,
+        resident_conv<C, HI, WI, MTI, SI::NT, NT, false, false, SI::PITCH>(smem, B_OFF, A_OFF, false, a.w[4], nullptr,
                                                                 a.g_prev + big_img, lmi, n0, lane);
         if (a.has_post) {
             // ---- the previous stack's gated transposed blocks on g_prev: A -> B, B -> A (+= A), twice; g0 ends in A.
@@ -888,7 +980,7 @@ __global__ __launch_bounds__(NW * NSPLIT * 64) void stack_full_bwd_kernel(StackF
 #pragma unroll 1
             for (int layer = 0; layer < 4; ++layer) {
                 const int odd = layer & 1;
-                resident_conv<C, HI, WI, MTI, SI::NT, NT, false, true>(smem, odd ? B_OFF : A_OFF, odd ? A_OFF : B_OFF, odd != 0,
+                resident_conv<C, HI, WI, MTI, SI::NT, NT, false, true, SI::PITCH>(smem, odd ? B_OFF : A_OFF, odd ? A_OFF : B_OFF, odd != 0,
                                                                        a.post_w[layer], nullptr, a.post_save[layer] + big_img,
                                                                        lmi, n0, lane, a.post_mask[layer] + big_img);
             }
@@ -899,8 +991,9 @@ __global__ __launch_bounds__(NW * NSPLIT * 64) void stack_full_bwd_kernel(StackF
 template <int C, int HI, int WI, int MTI, int HO, int WO, int MTO, int NW, int NSPLIT>
 int launch_stack_full_bwd(const StackFullBwdArgs &args, hipStream_t st)
 {
-    using SI = StackCfg<C, HI, WI, MTI, NW, NSPLIT>;
+    using SI = StackCfg<C, HI, WI, MTI, NW, NSPLIT, WI + 1>;  // the kernel's own padded layout
     constexpr size_t kLds = 2 * (size_t)SI::LDS_MAP * 4;
+    static_assert(kLds <= 160 * 1024, "two padded maps fit the CU's LDS");
     constexpr auto kern = stack_full_bwd_kernel<C, HI, WI, MTI, HO, WO, MTO, NW, NSPLIT>;
     if (int rc = prepare_kernel<kern>("stack_full_bwd", kLds)) return rc;
     const int grid = args.n_images < 256 ? args.n_images : 256;  // one workgroup per CU (LDS)
