@@ -791,6 +791,27 @@ int ppo_replay_pairwise_sqdist_u8(const uint8_t *data, int64_t n_rows, int64_t D
                                   void *stream);
 
 /* ------------------------------------------------------------------------
+ * Gradient-noise diagnostics: the simple noise scale of rl/sns.py (estimate_noise_scale :149-178, with the norms of
+ * rl/utils.py:146-161).  An estimate runs `passes` backward passes; each overwrites the flat gradient `grad` [n].
+ *
+ * ppo_grad_noise_workspace_bytes(max_passes): bytes of `workspace` for estimates of up to max_passes passes (0 when
+ *   max_passes < 1).
+ * ppo_grad_noise_pass_f32 - one launch behind backward pass number `pass`:
+ *   acc[i] = grad[i] (pass 0) or acc[i] += grad[i] (float32, element-wise, the rounding of ppo_accumulate_f32 and of the
+ *   reference's `acc += p`), and from the same read the pass's sum of grad[i]^2 in float64 (float32 squares are exact
+ *   there, only the summation rounds), left as per-workgroup partials in row `pass` of the workspace.
+ * ppo_grad_noise_finish_f64 - two launches after the last pass: out[0..passes) = each pass's sum of grad^2,
+ *   out[passes] = sum of acc^2; `out` holds passes + 1 doubles (device), to be read in one copy.
+ * Every sum has a fixed order (no atomics, no dependence on workgroup arrival): equal inputs give equal bits.  grad and
+ * acc may sit at any 4-byte-aligned address, independently; n >= 1.  PPO_E_INVALID (before any HIP call) on a null
+ * pointer, n < 1, pass outside [0, max_passes), passes outside [1, max_passes]; PPO_E_ALIGN on a misaligned pointer.
+ * ---------------------------------------------------------------------- */
+size_t ppo_grad_noise_workspace_bytes(int max_passes);
+int ppo_grad_noise_pass_f32(const float *grad, float *acc, int64_t n, int pass, int max_passes, void *workspace, void *stream);
+int ppo_grad_noise_finish_f64(const float *acc, int64_t n, int passes, int max_passes, void *workspace, double *out,
+                              void *stream);
+
+/* ------------------------------------------------------------------------
  * Synthetic vectorised environment (HOST pointers; runs on host threads).
  * The benchmark workload of SURVEY.md §8(d): obs uint8 i.i.d. uniform, reward ~ N(0,1),
  * done ~ Bernoulli(p_done), auto-reset; stands where the reference has the

@@ -165,6 +165,9 @@ SIGNATURES = {
     "ppo_replay_scatter_rows": (_i, [_vp, _vp, _i64, _i64, _vp, _vp, _i, _vp, _vp, _i64, _vp]),
     "ppo_replay_gather_rows2": (_i, [_vp, _vp, _i64, _vp, _vp, _i64, _i64, _vp, _i, _vp, _vp, _vp]),
     "ppo_replay_pairwise_sqdist_u8": (_i, [_vp, _i64, _i64, _vp, _i, _vp, _vp]),
+    "ppo_grad_noise_workspace_bytes": (_sz, [_i]),
+    "ppo_grad_noise_pass_f32": (_i, [_vp, _vp, _i64, _i, _i, _vp, _vp]),
+    "ppo_grad_noise_finish_f64": (_i, [_vp, _i64, _i, _i, _vp, _vp, _vp]),
 }
 
 class PackJob(ctypes.Structure):

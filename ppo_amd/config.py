@@ -5,8 +5,9 @@ singleton read at call time; grouped flags appear as `--<prefix>_<name>` and are
 `args.<prefix>.<name>`, rl/config.py:38-185).  Defaults cite rl/config.py line numbers.
 Flags of out-of-scope subsystems are accepted and ignored with a
 note, so existing launch lines keep working.  The `hash` group is registered only on a launch line that enables hashing
-(`--hash_enabled[=True]`), the `replay` group only on one that names a `--replay_mode` other than `off`: every other line
-parses exactly as it did before state hashing and the replay buffer were built.
+(`--hash_enabled[=True]`), the `replay` group only on one that names a `--replay_mode` other than `off`, the `sns` group
+only on one that enables noise-scale estimation (`--sns_enabled[=True]`): every other line parses exactly as it did before
+state hashing, the replay buffer and the simple noise scale were built.
 """
 import argparse
 import sys
@@ -179,16 +180,14 @@ class HashConfig(_Group):  # rl/config.py:412-429
     )
 
 
-def hashing_enabled_on(argv):
-    """Whether a launch line enables state hashing somewhere: a `--hash_enabled`, `--hash_enabled=<true>` or
-    `--hash_enabled <true>` on it.  (A later `--hash_enabled=False` on such a line is then the parser's to resolve: the
-    last one wins, and verify() refuses a bonus that is left without hashing.)"""
+def _flag_enabled_on(argv, flag):
+    """Whether a launch line holds the boolean `flag` with a true value: `flag`, `flag=<true>` or `flag <true>`."""
     for i, a in enumerate(argv):
         value = None
-        if a == "--hash_enabled":
+        if a == flag:
             nxt = argv[i + 1] if i + 1 < len(argv) else None
             value = "true" if nxt is None or nxt.startswith("--") else nxt
-        elif a.startswith("--hash_enabled="):
+        elif a.startswith(flag + "="):
             value = a.split("=", 1)[1]
         if value is not None:
             try:
@@ -197,6 +196,64 @@ def hashing_enabled_on(argv):
             except argparse.ArgumentTypeError:
                 return True  # the parser reports the bad value
     return False
+
+
+def hashing_enabled_on(argv):
+    """Whether a launch line enables state hashing somewhere: a `--hash_enabled`, `--hash_enabled=<true>` or
+    `--hash_enabled <true>` on it.  (A later `--hash_enabled=False` on such a line is then the parser's to resolve: the
+    last one wins, and verify() refuses a bonus that is left without hashing.)"""
+    return _flag_enabled_on(argv, "--hash_enabled")
+
+
+class SimpleNoiseScaleConfig(_Group):  # rl/config.py:188-206
+    LABELS = ("policy", "distil", "value", "value_heads")
+    FIELDS = (
+        ("enabled", bool, False, "simple noise scale estimates (critical batch size) of the update phases"),
+        # the reference's default is this list, which its own ast.literal_eval cannot take; a string is parsed
+        ("labels", str, ["policy", "distil", "value", "value_heads"], "value|value_heads|distil|policy"),
+        ("period", int, 3, "generate estimates every n updates"),
+        ("max_heads", int, 7, "limit to this number of heads when doing per head noise estimate"),
+        ("b_big", int, 2048, "rows of the large batch"),
+        ("b_small", int, 128, "rows of the small batch"),
+        ("fake_noise", bool, False, "also log estimates of synthetic gradients whose noise follows the horizon"),
+        ("smoothing_mode", str, "ema", "[ema|avg]"),
+        # the reference types these int and so cannot parse its own defaults (0.2e6) from a command line
+        ("smoothing_horizon_avg", float, 1e6, "how big to make the averaging window (env steps)"),
+        ("smoothing_horizon_s", float, 0.2e6, "how much to smooth s"),
+        ("smoothing_horizon_g2", float, 1.0e6, "how much to smooth g2"),
+        ("smoothing_horizon_policy", float, 5e6, "how much to smooth g2 for policy (normally much higher)"),
+    )
+
+    def __init__(self, prefix):
+        super().__init__(prefix)
+        self.labels = list(self.labels)  # a list of this instance's own, not the one FIELDS holds
+
+    def update(self, ns):
+        super().update(ns)
+        if not isinstance(self.labels, str):
+            self.labels = list(self.labels)
+
+    def label_list(self):
+        """The labels as a list: the default list as it is, a string through ast.literal_eval (rl/sns.py:294)."""
+        import ast
+        labels = self.labels
+        if isinstance(labels, str):
+            try:
+                labels = ast.literal_eval(labels)
+            except (ValueError, SyntaxError):
+                raise ValueError(f"--sns_labels={self.labels}: a Python list of labels, such as \"['policy', 'value']\", "
+                                 "or one quoted label") from None
+        if isinstance(labels, str):
+            labels = [labels]
+        if not isinstance(labels, (list, tuple)):
+            raise ValueError(f"--sns_labels={self.labels}: a list of labels")
+        return [str(x).lower() for x in labels]
+
+
+def sns_enabled_on(argv):
+    """Whether a launch line enables noise-scale estimation (`--sns_enabled[=True]`): only then are the `sns` flags
+    registered."""
+    return _flag_enabled_on(argv, "--sns_enabled")
 
 
 class ReplayConfig(_Group):  # rl/config.py:357-375
@@ -251,6 +308,7 @@ class Config:
         self.ir = IRConfig("ir")
         self.hash = HashConfig("hash")  # not in _groups: registered per launch line (setup)
         self.replay = ReplayConfig("replay")  # likewise
+        self.sns = SimpleNoiseScaleConfig("sns")  # likewise
         # (a flag belongs to the group with the longest matching prefix: rnd_opt_lr is rnd_opt's, rnd_enabled is rnd's)
         self._groups = (self.policy_opt, self.value_opt, self.distil_opt, self.distil, self.model, self.env, self.tvf,
                         self.rnd_opt, self.rnd, self.ir)
@@ -396,7 +454,9 @@ class Config:
         # (ignored with a note, in command-line order) and args.hash holds the defaults
         self.hash = HashConfig("hash")
         self.replay = ReplayConfig("replay")  # the same for the replay flags and a --replay_mode other than off
-        optional = ((self.hash,) if hashing_enabled_on(argv) else ()) + ((self.replay,) if replay_mode_on(argv) else ())
+        self.sns = SimpleNoiseScaleConfig("sns")  # and for the sns flags and --sns_enabled
+        optional = ((self.hash,) if hashing_enabled_on(argv) else ()) + ((self.replay,) if replay_mode_on(argv) else ()) \
+            + ((self.sns,) if sns_enabled_on(argv) else ())
         groups = self._groups + optional
         for g in optional:
             g.add(parser)
@@ -445,6 +505,22 @@ class Config:
                 raise ValueError(f"--replay_mode={self.replay.mode} needs a --replay_size > 0")
             if not 0 < self.replay.thinning <= 1:
                 raise ValueError(f"--replay_thinning={self.replay.thinning}: a fraction in (0, 1]")
+        if self.sns.enabled:
+            if self.sns.smoothing_mode not in ("ema", "avg"):
+                raise ValueError(f"Invalid smoothing mode {self.sns.smoothing_mode}.")
+            bad = [x for x in self.sns.label_list() if x not in SimpleNoiseScaleConfig.LABELS]
+            if bad:
+                raise ValueError(f"--sns_labels: {bad} not in policy | value | distil | value_heads")
+            if self.sns.period < 1 or self.sns.b_small < 1:
+                raise ValueError("--sns_period and --sns_b_small must be at least 1")
+            # b_small must divide b_big (rl/sns.py:146, 198; asserted there in the middle of an update): the rollout for
+            # `policy`, --sns_b_big for every other label
+            labels = self.sns.label_list()
+            if "policy" in labels and self.batch_size % self.sns.b_small:
+                raise ValueError(f"--sns_b_small={self.sns.b_small} must divide the rollout, n_steps x agents = "
+                                 f"{self.batch_size}, which is the policy estimate's b_big")
+            if set(labels) - {"policy"} and self.sns.b_big % self.sns.b_small:
+                raise ValueError(f"--sns_b_small={self.sns.b_small} must divide --sns_b_big={self.sns.b_big}")
         # EnvConfig.auto (rl/config.py:563-600)
         if self.env.frame_skip in (None, -1):
             self.env.frame_skip = 4 if self.env.type == "atari" else 1
@@ -475,7 +551,8 @@ class Config:
     def flatten(self):
         d = {k: v for k, v in vars(self).items() if not k.startswith("_") and not isinstance(v, _Group)}
         d["use_intrinsic_rewards"] = self.use_intrinsic_rewards
-        for g in self._groups + ((self.hash,) if self.hash.enabled else ()) + ((self.replay,) if self.replay.enabled else ()):
+        for g in self._groups + ((self.hash,) if self.hash.enabled else ()) + ((self.replay,) if self.replay.enabled else ()) \
+                + ((self.sns,) if self.sns.enabled else ()):
             d.update(g.flatten())
         return d
 

@@ -35,11 +35,12 @@ What changed relative to the reference, and why (MI355X-first):
 """
 import copy
 import math
+import time
 
 import numpy as np
 import torch
 
-from . import _lib, parallel, value_quality
+from . import _lib, parallel, sns, value_quality
 from .config import args
 from .models import AdamState
 from .returns import calculate_bootstrapped_returns
@@ -127,6 +128,11 @@ class Runner:
         if args.replay.enabled and self.world > 1:
             raise NotImplementedError("experience replay under data parallelism is not built (every rank would keep a buffer "
                                       "of its own env columns and draw its own distil batch)")
+        if args.sns.enabled and self.world > 1:
+            raise NotImplementedError("noise-scale estimation under data parallelism is not built (a rank's gradients are not the batch's)")
+        # simple noise scale (rl/rollout.py:177): smoothed estimates per label, filled by ppo_amd/sns.py when --sns_enabled
+        self.noise_stats = {}
+        self._tvf_subset_weight_cache = {}
         N, A, nA, VH, dev = self.N, self.A, self.n_actions, self.VH, self.device
         gaussian = action_dist == "gaussian"
         obs_dtype = torch.uint8 if model.policy_net.encoder_kind in ("impala", "nature") and args.env.type != "mujoco" else torch.float32
@@ -995,6 +1001,29 @@ class Runner:
             """Also the exit path of a failed step: the parked hook must come back whatever happened."""
             self.net.grad_ready_hook = self.hook
 
+    def _noise_pass(self, net, step_fn, obs_all):
+        """step(index) for a noise-scale estimate (ppo_amd/sns.py): one forward + backward pass of a phase's minibatch
+        step `step_fn` with loss_scale 1 on the rows `index` of the batch `obs_all` [B, *state_shape], through the input
+        form the phase's epochs use (_run_epochs): the fused MLP index read, the in-conv index read, or a gather launch.
+        The per-sample statistics are dropped."""
+        B = int(obs_all.shape[0])
+        obs_rows = obs_all.view(B, -1)
+        row_bytes = obs_rows.shape[1] * obs_rows.element_size()
+        fused = bool(getattr(net, "mlp_fused", False)) and net.obs_norm is None and self.all_obs.dtype == torch.float32
+        in_conv = not fused and hasattr(net, "takes_obs_index") and net.takes_obs_index(self.all_obs)
+
+        def one_pass(idx):
+            if fused:
+                step_fn(obs_rows, idx, 1.0, stat_sums=None, stat_accumulate=False, obs_indexed=True)
+            elif in_conv:
+                step_fn(obs_all, idx, 1.0, obs_indexed=True)
+            else:
+                rows = int(idx.shape[0])
+                mb_obs = net._buf("mb_obs", (rows, *self.state_shape), self.all_obs.dtype)
+                self._call("ppo_gather_rows", _p(obs_rows), row_bytes, B, _p(idx), rows, _p(mb_obs))
+                step_fn(mb_obs, idx, 1.0)
+        return one_pass
+
     def _run_epochs(self, label, optimizer, epochs, mini_batch_size, step_fn, n_stats, rows=None, obs=None):
         """Permutation minibatching over the rollout (rl/rollout.py:2257-2407): per epoch one host shuffle
         (np.random, as the reference :2319-2320); per minibatch — in micro-batches of at most --max_micro_batch_size
@@ -1029,6 +1058,12 @@ class Runner:
         mb_obs = None if (fused or in_conv) else net._buf("mb_obs", (micro, *self.state_shape), self.all_obs.dtype)
         stat_rows = net._buf(f"stat_rows_{label}", (epochs * n_mb, n_stats))
         norm_rows = net._buf(f"norm_rows_{label}", (epochs * n_mb,))
+        if args.sns.enabled and epochs > 0 and sns.wants_noise_estimate(self, label):
+            # noise of the first update only, before epoch 0's shuffle (rl/rollout.py:2290-2294)
+            start_time = time.time()
+            sns.estimate_noise_scale(self, B, self._noise_pass(net, step_fn, obs_all), net, label)
+            self.log.watch_mean(f"sns_time_{label}", (time.time() - start_time) / args.sns.period, display_width=8,
+                                display_name=f"t_s{label[:3]}")
         k = 0
         for _epoch in range(epochs):
             ordering = np.arange(B, dtype=np.int32)
@@ -1104,6 +1139,22 @@ class Runner:
             return net.value_minibatch(mb_obs, returns=returns, tvf_returns=tvf_returns, tvf_weights=weights,
                                        vf_coef=args.ppo_vf_coef, tvf_coef=args.tvf.coef, loss_scale=loss_scale, index=idx,
                                        tvf_keep_prob=keep, dropout_seed=seed, dropout_offset=off, **kw)
+
+        if args.sns.enabled and self.tvf is not None and sns.wants_noise_estimate(self, "value_heads") \
+                and args.sns.max_heads > 0:
+            # per-horizon noise estimates (rl/rollout.py:1981-1990): the TVF loss alone on heads 0..head
+            def make_step(head):
+                subset = self._tvf_subset_weights(self._required_tvf_heads(-head))
+
+                def head_step(mb_obs, idx, loss_scale, **kw):
+                    off = self.tvf.next_dropout_offset(idx.shape[0] * self.K) if keep < 1.0 else 0
+                    return net.value_minibatch(mb_obs, returns=None, tvf_returns=tvf_returns, tvf_weights=subset,
+                                               vf_coef=args.ppo_vf_coef, tvf_coef=args.tvf.coef, loss_scale=loss_scale,
+                                               index=idx, tvf_keep_prob=keep, dropout_seed=seed, dropout_offset=off, **kw)
+                return self._noise_pass(net, head_step, self.all_obs[:self.N].view(B, *self.state_shape))
+            sns.log_accumulated_gradient_norms(self, make_step, net)
+            if args.sns.fake_noise:
+                sns.log_fake_accumulated_gradient_norms(self, net.n_parameters())
         self._run_epochs("value", self.value_optimizer, args.value_opt.epochs, args.value_opt.mini_batch_size, step, 4)
 
     def wants_distil_update(self, location=None):
@@ -1259,10 +1310,29 @@ class Runner:
         s = stats.double().mean(0).cpu().numpy()
         return {"loss": float(-s[6] * loss_scale), "kl_approx": float(s[4]), "kl_true": float(s[5]), "clip_frac": float(s[3])}
 
+    @staticmethod
+    def _required_tvf_heads(single_value_head):
+        """rl/rollout.py:1518-1524: None -> all heads, h >= 0 -> [h], h < 0 -> heads 0..-h."""
+        if single_value_head is None:
+            return None
+        return [int(single_value_head)] if single_value_head >= 0 else list(range(-int(single_value_head) + 1))
+
+    def _tvf_subset_weights(self, heads):
+        """The device weight vector that trains the TVF heads `heads` alone (tvf.subset_head_weights), cached per set."""
+        from .tvf import subset_head_weights
+        key = tuple(heads)
+        dev = self._tvf_subset_weight_cache.get(key)
+        if dev is None:
+            dev = torch.as_tensor(subset_head_weights(self.tvf_weights, heads), device=self.device)
+            self._tvf_subset_weight_cache[key] = dev
+        return dev
+
     def train_value_minibatch(self, data, loss_scale=1.0, single_value_head=None):
-        if single_value_head is not None:
-            raise NotImplementedError("training a single TVF head (noise-scale estimation) is out of scope")
-        weights = self._tvf_value_weights_dev if "tvf_returns" in data else None
+        """rl/rollout.py:1513-1567.  single_value_head: train the TVF head h alone (h >= 0) or heads 0..-h (h < 0)."""
+        heads = self._required_tvf_heads(single_value_head)
+        weights = None
+        if "tvf_returns" in data:
+            weights = self._tvf_value_weights_dev if heads is None else self._tvf_subset_weights(heads)
         stats = self.value_net.value_minibatch(data["prev_state"], returns=data.get("returns"),
                                                tvf_returns=data.get("tvf_returns"), tvf_weights=weights,
                                                vf_coef=args.ppo_vf_coef, tvf_coef=args.tvf.coef, loss_scale=loss_scale)
@@ -1443,6 +1513,8 @@ class Runner:
             rms = self.intrinsic_returns_rms
             data["intrinsic_returns_rms"] = {"mean": np.float64(rms.mean), "var": np.float64(rms.var),
                                              "count": float(rms.count)}
+        if args.sns.enabled:
+            data["noise_stats"] = sns.noise_stats_to_plain(self.noise_stats)  # rl/rollout.py:428-429, as plain data
         if self.hash is not None:
             data.update(self.hash.state_dict())  # rl/rollout.py:409-411: hash_global_counts, hash_recent_counts
         if self.replay_buffer is not None and not disable_replay:
@@ -1467,6 +1539,8 @@ class Runner:
             self.ems_norm = np.asarray(cp["ems_norm"], np.float64).copy()
             rms = cp["intrinsic_returns_rms"]
             self.intrinsic_returns_rms.restore_state((np.float64(rms["mean"]), np.float64(rms["var"]), rms["count"]))
+        if args.sns.enabled:  # rl/rollout.py:495
+            self.noise_stats = sns.noise_stats_from_plain(cp.get("noise_stats"), self)
         if self.hash is not None:  # rl/rollout.py:500-502
             self.hash.load_state_dict(cp)
         if self.replay_buffer is not None:  # rl/rollout.py:504-505

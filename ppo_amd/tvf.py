@@ -33,6 +33,21 @@ def get_value_head_horizons(n_heads: int, max_horizon: int, spacing: str = "geom
     return (horizons, multiplicity.astype(np.float32)) if include_weight else horizons
 
 
+def subset_head_weights(weights, heads) -> np.ndarray:
+    """Per-head weights [K] float32 under which the value-loss kernels - which form K^-1/2 sum_k w'_k l_k over all K
+    heads - give the reference's loss over the heads S alone, |S|^-1/2 sum_{k in S} w_k l_k (rl/tvf.py:45-73 with
+    required_tvf_heads = S): w'_k = w_k sqrt(K / |S|) for k in S, else 0.  `weights`: the duplicate-removal weights
+    (the h_weighting is skipped when heads are named, :56).  The factor is formed in float64 and rounded once."""
+    w = np.asarray(weights, np.float64)
+    K = len(w)
+    heads = [int(h) for h in heads]
+    if not heads or min(heads) < 0 or max(heads) >= K or len(set(heads)) != len(heads):
+        raise ValueError(f"TVF heads {heads}: distinct indices in [0, {K})")
+    out = np.zeros(K, np.float64)
+    out[heads] = w[heads] * math.sqrt(K / len(heads))
+    return out.astype(np.float32)
+
+
 def horizon_interpolate(horizons: np.ndarray, values: np.ndarray, target_horizons: np.ndarray):
     """Linear interpolation of values[..., K] (given at sorted `horizons`, horizons[0] == 0) at one target
     horizon per example; targets are clamped to the horizon range and h <= 0 has value 0 by definition."""

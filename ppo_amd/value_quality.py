@@ -9,7 +9,7 @@ lives on and fetched in one copy; the explained-variance block runs on a quarter
 import numpy as np
 import torch
 
-CURVE_MAX_HEADS = 7  # args.sns.max_heads (rl/config.py:195): the curve diagnostics look at <= 7 horizons
+from .config import args
 
 
 def explained_variance(ypred, y, bias: float = 0.0) -> float:
@@ -89,9 +89,12 @@ def log_dna_value_quality(log, values, targets):
     return ev
 
 
-def log_curve_quality(log, estimates, targets, horizons, postfix: str = "", max_heads: int = CURVE_MAX_HEADS):
-    """Explained variance of the truncated-value curve at up to max_heads horizons, plus first / mid / last and the
-    variance-weighted average (rl/rollout.py:1038-1110).  estimates, targets: [N, A, K]."""
+def log_curve_quality(log, estimates, targets, horizons, postfix: str = "", max_heads: int = None):
+    """Explained variance of the truncated-value curve at up to max_heads horizons (default --sns_max_heads, 7:
+    rl/rollout.py:1093), plus first / mid / last and the variance-weighted average (rl/rollout.py:1038-1110).
+    estimates, targets: [N, A, K]."""
+    if max_heads is None:
+        max_heads = args.sns.max_heads
     estimates, targets = _host(estimates), _host(targets)
     K = estimates.shape[-1]
     est, tgt = estimates.reshape(-1, K), targets.reshape(-1, K)
