@@ -233,20 +233,42 @@ __global__ __launch_bounds__((NW * 64), 4) void conv3x3_block_kernel(
     }
 }
 
+struct BlockArgs {
+    const float *in, *w0, *b0, *w1, *b1;
+    float *out;
+    int n;
+    hipStream_t st;
+};
+
 template <int C, int H, int W, int TR, int NW>
-int launch_block(const float *in, const float *w0, const float *b0, const float *w1, const float *b1, float *out, int n,
-                 hipStream_t st)
+int launch_block(const BlockArgs &a)
 {
     using S = BlockCfg<C, H, W, TR, NW>;
     constexpr auto kern = conv3x3_block_kernel<C, H, W, TR, NW>;
     int nb = 0;
     if (int rc = prepare_kernel<kern>("conv3x3_block", S::LDS_BYTES, NW * 64, &nb)) return rc;
     const int wg_per_cu = nb < 1 ? 1 : (nb > 3 ? 3 : nb);
-    const int n_items = n * S::NBANDS;
+    const int n_items = a.n * S::NBANDS;
     int grid = 256 * wg_per_cu;
     if (grid > n_items) grid = n_items;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), S::LDS_BYTES, st, in, w0, b0, w1, b1, out, n);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), S::LDS_BYTES, a.st, a.in, a.w0, a.b0, a.w1, a.b1, a.out, a.n);
     return check_launch("conv3x3_block_kernel");
+}
+
+// The one case list.  Without arguments (a == nullptr) it launches nothing and answers PPO_OK / PPO_E_INVALID: the probe.
+// At most two half-image items per CU: half images on 16 waves (1.1 x the MFMA work of the two convolutions: conv0's
+// two halo rows and the last tile); more images: bands of TR rows on 8 waves, two workgroups per CU (1.3 x, but the
+// next item's staging runs under the other workgroup's K loops)
+int dispatch_block(int channels, int h, int w, const BlockArgs *a)
+{
+#define PPO_BLOCK_CASE(C, H, W, TR_HALF, TR_BAND)                                                                       \
+    if (channels == C && h == H && w == W)                                                                              \
+        return !a ? PPO_OK : a->n <= PPO_TUNE_BLOCK_HALF_MAX ? launch_block<C, H, W, TR_HALF, 16>(*a) : launch_block<C, H, W, TR_BAND, 8>(*a);
+    PPO_BLOCK_CASE(16, 42, 42, 21, 6)
+    PPO_BLOCK_CASE(16, 32, 32, 16, 8)
+#undef PPO_BLOCK_CASE
+    return a ? fail(PPO_E_INVALID, "ppo_conv3x3_block_forward_packed_f32: no kernel for %d channels at %dx%d", channels, h, w)
+             : PPO_E_INVALID;
 }
 
 }  // namespace
@@ -254,7 +276,7 @@ int launch_block(const float *in, const float *w0, const float *b0, const float 
 
 extern "C" int ppo_conv3x3_block_supported(int channels, int h, int w)
 {
-    return channels == 16 && ((h == 42 && w == 42) || (h == 32 && w == 32));
+    return ppo::dispatch_block(channels, h, w, nullptr) == PPO_OK;
 }
 
 extern "C" int ppo_conv3x3_block_forward_packed_f32(const float *in, const float *packed0, const float *bias0,
@@ -268,15 +290,6 @@ extern "C" int ppo_conv3x3_block_forward_packed_f32(const float *in, const float
         return fail(PPO_E_INVALID, "ppo_conv3x3_block_forward_packed_f32: null pointer");
     if (!aligned(packed0, 16) || !aligned(packed1, 16))
         return fail(PPO_E_ALIGN, "ppo_conv3x3_block_forward_packed_f32: packed weights must be 16-byte aligned");
-    hipStream_t st = as_stream(stream);
-    // at most two half-image items per CU: half images on 16 waves (1.1 x the MFMA work of the two convolutions: conv0's
-    // two halo rows and the last tile); more images: bands of TR rows on 8 waves, two workgroups per CU (1.3 x, but the
-    // next item's staging runs under the other workgroup's K loops)
-    if (channels == 16 && h == 42 && w == 42)
-        return n <= PPO_TUNE_BLOCK_HALF_MAX ? launch_block<16, 42, 42, 21, 16>(in, packed0, bias0, packed1, bias1, out, n, st)
-                                            : launch_block<16, 42, 42, 6, 8>(in, packed0, bias0, packed1, bias1, out, n, st);
-    if (channels == 16 && h == 32 && w == 32)
-        return n <= PPO_TUNE_BLOCK_HALF_MAX ? launch_block<16, 32, 32, 16, 16>(in, packed0, bias0, packed1, bias1, out, n, st)
-                                            : launch_block<16, 32, 32, 8, 8>(in, packed0, bias0, packed1, bias1, out, n, st);
-    return fail(PPO_E_INVALID, "ppo_conv3x3_block_forward_packed_f32: no kernel for %d channels at %dx%d", channels, h, w);
+    const BlockArgs a{in, packed0, bias0, packed1, bias1, out, n, as_stream(stream)};
+    return dispatch_block(channels, h, w, &a);
 }

@@ -601,7 +601,8 @@ struct WgradArgs {
     int *n_slabs_out = nullptr;          // slabs only: the caller reduces them later (ppo_conv3x3_wgrad_reduce_f32)
     const WgradBatch *more = nullptr;    // `count` problems of one geometry, each with a workspace of ws_bytes
     int count = 1;
-    const uint8_t *argmax = nullptr;     // the pooled-gradient kernels (WgradBatch::argmax)
+    bool pooled = false;                 // pick a pooled-gradient kernel: dy is the POOLED gradient and ...
+    const uint8_t *argmax = nullptr;     // ... argmax says where each element of it goes (WgradBatch::argmax)
     const int32_t *in_index = nullptr;   // uint8 input only, nullable (WgradBatch::in_index)
     hipStream_t st = nullptr;
 };
@@ -660,15 +661,18 @@ int dispatch_wgrad(int cin, int cout, int h, int w_, const WgradArgs &a)
 {
 #define PPO_WGRAD_POOLED_CASE(CI, CO, HH, WW, TR)                                                    \
     if constexpr (IN_MODE != IN_RELU) {                                                              \
-        if (a.argmax && cin == CI && cout == CO && h == HH && w_ == WW)                              \
+        if (a.pooled && cin == CI && cout == CO && h == HH && w_ == WW) {                            \
+            if (a.probe) return PPO_OK;                                                              \
             return launch_wgrad<CI, CO, HH, WW, TR, IN_MODE, true>(a);                               \
+        }                                                                                            \
     }
     PPO_WGRAD_POOLED_CASE(4, 16, 84, 84, 6)
     PPO_WGRAD_POOLED_CASE(5, 16, 84, 84, 6)
     PPO_WGRAD_POOLED_CASE(3, 16, 64, 64, 8)
     PPO_WGRAD_POOLED_CASE(4, 16, 64, 64, 8)
 #undef PPO_WGRAD_POOLED_CASE
-    if (a.argmax)
+    if (a.pooled && a.probe) return PPO_E_INVALID;
+    if (a.pooled)
         return fail(PPO_E_INVALID, "conv3x3_wgrad: no pooled-gradient kernel for cin=%d cout=%d h=%d w=%d in_mode=%d", cin,
                     cout, h, w_, IN_MODE);
 #define PPO_WGRAD_CASE(ALLOWED, CI, CO, HH, WW, TR)                                                  \
@@ -715,13 +719,35 @@ int wgrad_slabs_pooled(const char *who, const void *in, const int32_t *index, in
     if (n <= 0) return fail(PPO_E_INVALID, "%s: n must be positive", who);
     if (!in || !g || !argmax || !workspace || !n_slabs) return fail(PPO_E_INVALID, "%s: null pointer", who);
     WgradArgs a;
-    a.in = in, a.in_index = index, a.dy = g, a.argmax = argmax, a.n = n, a.n_slabs_out = n_slabs, a.st = as_stream(stream);
+    a.in = in, a.in_index = index, a.dy = g, a.pooled = true, a.argmax = argmax, a.n = n, a.n_slabs_out = n_slabs, a.st = as_stream(stream);
     a.ws = static_cast<float *>(workspace), a.ws_bytes = workspace_bytes;
     const int rc = with_in_mode(in_mode, [&](auto mode) {
         if constexpr (decltype(mode)::value == IN_RELU) return (int)kNoSuchMode;
         else return dispatch_wgrad<decltype(mode)::value>(cin, cout, h, w, a);
     });
     return rc == kNoSuchMode ? fail(PPO_E_INVALID, "%s: in_mode %d has no pooled-gradient kernel", who, in_mode) : rc;
+}
+
+// ppo_conv3x3_backward_weight_slabs_batch_f32 and, with a ReLU flag per problem (`mixed`, in_mode IN_RELU), its _mixed sibling
+int wgrad_slabs_batch(const char *who, const void *const *ins, int in_mode, bool mixed, const int *relu, const float *const *dys,
+                      void *const *workspaces, size_t workspace_bytes, int count, int n, int cin, int cout, int h, int w,
+                      int *n_slabs, void *stream)
+{
+    if (n <= 0 || count < 1 || count > kWgradBatch)
+        return fail(PPO_E_INVALID, "%s: n must be positive, count in 1..%d", who, kWgradBatch);
+    if (!ins || (mixed && !relu) || !dys || !workspaces || !n_slabs) return fail(PPO_E_INVALID, "%s: null pointer", who);
+    WgradBatch b{};
+    for (int k = 0; k < count; ++k) {
+        if (!ins[k] || !dys[k] || !workspaces[k]) return fail(PPO_E_INVALID, "%s: null pointer in problem %d", who, k);
+        b.in[k] = ins[k];
+        b.dy[k] = dys[k];
+        b.partial[k] = static_cast<float *>(workspaces[k]);
+        if (mixed) b.relu_floor[k] = relu[k] ? 0.f : -__builtin_inff();
+    }
+    WgradArgs a;
+    a.more = &b, a.count = count, a.ws_bytes = workspace_bytes, a.n = n, a.n_slabs_out = n_slabs, a.st = as_stream(stream);
+    const int rc = dispatch_wgrad_mode(in_mode, cin, cout, h, w, a);
+    return rc == kNoSuchMode ? fail(PPO_E_INVALID, "%s: unknown in_mode %d", who, in_mode) : rc;
 }
 
 }  // namespace
@@ -775,23 +801,8 @@ extern "C" int ppo_conv3x3_backward_weight_slabs_batch_f32(const void *const *in
                                                            int n, int cin, int cout, int h, int w, int *n_slabs,
                                                            void *stream)
 {
-    using namespace ppo;
-    if (n <= 0 || count < 1 || count > kWgradBatch)
-        return fail(PPO_E_INVALID, "ppo_conv3x3_backward_weight_slabs_batch_f32: n must be positive, count in 1..%d", kWgradBatch);
-    if (!ins || !dys || !workspaces || !n_slabs)
-        return fail(PPO_E_INVALID, "ppo_conv3x3_backward_weight_slabs_batch_f32: null pointer");
-    WgradBatch b{};
-    for (int k = 0; k < count; ++k) {
-        if (!ins[k] || !dys[k] || !workspaces[k])
-            return fail(PPO_E_INVALID, "ppo_conv3x3_backward_weight_slabs_batch_f32: null pointer in problem %d", k);
-        b.in[k] = ins[k];
-        b.dy[k] = dys[k];
-        b.partial[k] = static_cast<float *>(workspaces[k]);
-    }
-    WgradArgs a;
-    a.more = &b, a.count = count, a.ws_bytes = workspace_bytes, a.n = n, a.n_slabs_out = n_slabs, a.st = as_stream(stream);
-    const int rc = dispatch_wgrad_mode(in_mode, cin, cout, h, w, a);
-    return rc == kNoSuchMode ? fail(PPO_E_INVALID, "ppo_conv3x3_backward_weight_slabs_batch_f32: unknown in_mode %d", in_mode) : rc;
+    return ppo::wgrad_slabs_batch("ppo_conv3x3_backward_weight_slabs_batch_f32", ins, in_mode, false, nullptr, dys, workspaces,
+                                  workspace_bytes, count, n, cin, cout, h, w, n_slabs, stream);
 }
 
 extern "C" int ppo_conv3x3_backward_weight_slabs_batch_mixed_f32(const void *const *ins, const int *relu, const float *const *dys,
@@ -799,23 +810,8 @@ extern "C" int ppo_conv3x3_backward_weight_slabs_batch_mixed_f32(const void *con
                                                                  int n, int cin, int cout, int h, int w, int *n_slabs,
                                                                  void *stream)
 {
-    using namespace ppo;
-    if (n <= 0 || count < 1 || count > kWgradBatch)
-        return fail(PPO_E_INVALID, "ppo_conv3x3_backward_weight_slabs_batch_mixed_f32: n must be positive, count in 1..%d", kWgradBatch);
-    if (!ins || !relu || !dys || !workspaces || !n_slabs)
-        return fail(PPO_E_INVALID, "ppo_conv3x3_backward_weight_slabs_batch_mixed_f32: null pointer");
-    WgradBatch b{};
-    for (int k = 0; k < count; ++k) {
-        if (!ins[k] || !dys[k] || !workspaces[k])
-            return fail(PPO_E_INVALID, "ppo_conv3x3_backward_weight_slabs_batch_mixed_f32: null pointer in problem %d", k);
-        b.in[k] = ins[k];
-        b.dy[k] = dys[k];
-        b.partial[k] = static_cast<float *>(workspaces[k]);
-        b.relu_floor[k] = relu[k] ? 0.f : -__builtin_inff();
-    }
-    WgradArgs a;
-    a.more = &b, a.count = count, a.ws_bytes = workspace_bytes, a.n = n, a.n_slabs_out = n_slabs, a.st = as_stream(stream);
-    return dispatch_wgrad<IN_RELU>(cin, cout, h, w, a);
+    return ppo::wgrad_slabs_batch("ppo_conv3x3_backward_weight_slabs_batch_mixed_f32", ins, ppo::IN_RELU, true, relu, dys, workspaces,
+                                  workspace_bytes, count, n, cin, cout, h, w, n_slabs, stream);
 }
 
 extern "C" int ppo_conv3x3_backward_weight_slabs_pooled_f32(const void *in, int in_mode, const float *g,
@@ -836,9 +832,13 @@ extern "C" int ppo_conv3x3_backward_weight_slabs_pooled_indexed_f32(const void *
                                    workspace_bytes, n, cin, cout, h, w, n_slabs, stream);
 }
 
+// The pooled cases of dispatch_wgrad in no-launch mode, for the two in_modes that have them (one list serves both).
 extern "C" int ppo_conv3x3_backward_weight_pooled_supported(int cin, int cout, int h, int w)
 {
-    return cout == 16 && ((h == 84 && w == 84 && (cin == 4 || cin == 5)) || (h == 64 && w == 64 && (cin == 3 || cin == 4)));
+    ppo::WgradArgs probe;
+    probe.probe = probe.pooled = true;
+    return ppo::dispatch_wgrad<ppo::IN_NONE>(cin, cout, h, w, probe) == PPO_OK ||
+           ppo::dispatch_wgrad<ppo::IN_U8>(cin, cout, h, w, probe) == PPO_OK;
 }
 
 extern "C" int ppo_conv3x3_wgrad_reduce_f32(const ppo_wgrad_job *jobs, int n_jobs, void *stream)

@@ -472,45 +472,51 @@ int launch_split_win16(const SplitTailArgs &args, hipStream_t st)
     return check_launch("stack_win16_bf16x3_kernel");
 }
 
-int split_tail(const char *who, bool backward, const float *in, const void *packed, const float *const *bias_or_mask,
-               float *s0, float *s1, float *s2, float *s3, int n_images, int channels, int h, int w, void *stream,
-               uint8_t *const *signs = nullptr)
+// The family's one case list.  Without arguments (args == nullptr) it launches nothing and answers PPO_OK / PPO_E_INVALID:
+// the probe.  32 channels: (H, W, MT, NW) of stack_tail_bf16x3_kernel; 16 channels: (HI, W, NWIN, R, NW, MT) of the
+// windowed kernel.  21x21, 11x11 and 42x42 are the maps of 84x84 observations, 16x16, 8x8 and 32x32 those of 64x64 (procgen).
+template <bool BACKWARD>
+int dispatch_split_tail(const char *who, int channels, int h, int w, const SplitTailArgs *args, hipStream_t st)
+{
+#define PPO_SPLIT_TAIL32(H, W, ...) \
+    if (channels == 32 && h == H && w == W) return args ? launch_split_tail<32, H, W, __VA_ARGS__, BACKWARD>(*args, st) : PPO_OK;
+#define PPO_SPLIT_WIN16(H, W, ...) \
+    if (channels == 16 && h == H && w == W) return args ? launch_split_win16<H, W, __VA_ARGS__, BACKWARD>(*args, st) : PPO_OK;
+    PPO_SPLIT_TAIL32(21, 21, 7, 4)
+    PPO_SPLIT_TAIL32(11, 11, 2, 4)
+    PPO_SPLIT_TAIL32(16, 16, 4, 4)
+    PPO_SPLIT_TAIL32(8, 8, 1, 4)
+    PPO_SPLIT_WIN16(32, 32, 2, 20, 10, 4)
+    PPO_SPLIT_WIN16(42, 42, 2, 25, PPO_TUNE_W16_NW, PPO_TUNE_W16_MT)
+#undef PPO_SPLIT_TAIL32
+#undef PPO_SPLIT_WIN16
+    return args ? fail(PPO_E_INVALID, "%s: no kernel for %d channels at %dx%d", who, channels, h, w) : PPO_E_INVALID;
+}
+
+template <bool BACKWARD>
+int split_tail(const char *who, const float *in, const void *packed, const float *const *bias_or_mask, float *s0, float *s1,
+               float *s2, float *s3, int n_images, int channels, int h, int w, void *stream, uint8_t *const *signs = nullptr)
 {
     if (n_images < 0) return fail(PPO_E_INVALID, "%s: negative batch", who);
     if (n_images == 0) return PPO_OK;
-    if (!in || !packed || (!bias_or_mask && !(backward && signs)) || !s3 || !aligned(packed, 16))
+    if (!in || !packed || (!bias_or_mask && !(BACKWARD && signs)) || !s3 || !aligned(packed, 16))
         return fail(PPO_E_INVALID, "%s: null or misaligned pointer", who);
-    if (backward && (!s0 || !s1 || !s2)) return fail(PPO_E_INVALID, "%s: the backward pass writes all four gradient maps", who);
+    if (BACKWARD && (!s0 || !s1 || !s2)) return fail(PPO_E_INVALID, "%s: the backward pass writes all four gradient maps", who);
     SplitTailArgs args;
     args.in = in, args.w = static_cast<const bf16x8 *>(packed), args.n_images = n_images;
     for (int l = 0; l < 4; ++l) {
         args.sign[l] = signs ? signs[l] : nullptr;
-        if (backward && signs) {  // the sign maps stand in for the float gate maps
+        if (BACKWARD && signs) {  // the sign maps stand in for the float gate maps
             if (!signs[l]) return fail(PPO_E_INVALID, "%s: null sign map of layer %d", who, l);
             args.bias[l] = args.mask[l] = nullptr;
             continue;
         }
         if (!bias_or_mask[l]) return fail(PPO_E_INVALID, "%s: null bias / mask of layer %d", who, l);
-        args.bias[l] = backward ? nullptr : bias_or_mask[l];
-        args.mask[l] = backward ? bias_or_mask[l] : nullptr;
+        args.bias[l] = BACKWARD ? nullptr : bias_or_mask[l];
+        args.mask[l] = BACKWARD ? bias_or_mask[l] : nullptr;
     }
     args.save[0] = s0, args.save[1] = s1, args.save[2] = s2, args.save[3] = s3;
-    hipStream_t st = as_stream(stream);
-    if (channels == 32 && h == 21 && w == 21)
-        return backward ? launch_split_tail<32, 21, 21, 7, 4, true>(args, st) : launch_split_tail<32, 21, 21, 7, 4, false>(args, st);
-    if (channels == 32 && h == 11 && w == 11)
-        return backward ? launch_split_tail<32, 11, 11, 2, 4, true>(args, st) : launch_split_tail<32, 11, 11, 2, 4, false>(args, st);
-    // the procgen-shaped net (64x64 observations: 32x32, 16x16 and 8x8 maps)
-    if (channels == 32 && h == 16 && w == 16)
-        return backward ? launch_split_tail<32, 16, 16, 4, 4, true>(args, st) : launch_split_tail<32, 16, 16, 4, 4, false>(args, st);
-    if (channels == 32 && h == 8 && w == 8)
-        return backward ? launch_split_tail<32, 8, 8, 1, 4, true>(args, st) : launch_split_tail<32, 8, 8, 1, 4, false>(args, st);
-    if (channels == 16 && h == 32 && w == 32)
-        return backward ? launch_split_win16<32, 32, 2, 20, 10, 4, true>(args, st) : launch_split_win16<32, 32, 2, 20, 10, 4, false>(args, st);
-    if (channels == 16 && h == 42 && w == 42)
-        return backward ? launch_split_win16<42, 42, 2, 25, PPO_TUNE_W16_NW, PPO_TUNE_W16_MT, true>(args, st)
-                        : launch_split_win16<42, 42, 2, 25, PPO_TUNE_W16_NW, PPO_TUNE_W16_MT, false>(args, st);
-    return fail(PPO_E_INVALID, "%s: no kernel for %d channels at %dx%d", who, channels, h, w);
+    return dispatch_split_tail<BACKWARD>(who, channels, h, w, &args, as_stream(stream));
 }
 
 }  // namespace
@@ -520,8 +526,7 @@ extern "C" size_t ppo_impala_stack_tail_bf16x3_packed_bytes(void) { return (size
 
 extern "C" int ppo_impala_stack_tail_bf16x3_supported(int channels, int h, int w)
 {
-    return (channels == 32 && ((h == 21 && w == 21) || (h == 11 && w == 11) || (h == 16 && w == 16) || (h == 8 && w == 8))) ||
-           (channels == 16 && ((h == 42 && w == 42) || (h == 32 && w == 32)));
+    return ppo::dispatch_split_tail<false>(nullptr, channels, h, w, nullptr, nullptr) == PPO_OK;
 }
 
 extern "C" int ppo_impala_stack_tail_pack_bf16x3_jobs(const ppo_split_pack_job *jobs, int n_jobs, void *stream)
@@ -559,7 +564,7 @@ extern "C" int ppo_impala_stack_tail_forward_bf16x3(const float *in, const void 
                                                     float *q0, float *a1, float *q1, int n_images, int channels, int h, int w,
                                                     void *stream)
 {
-    return ppo::split_tail("ppo_impala_stack_tail_forward_bf16x3", false, in, packed, biases, a0, q0, a1, q1, n_images, channels, h,
+    return ppo::split_tail<false>("ppo_impala_stack_tail_forward_bf16x3", in, packed, biases, a0, q0, a1, q1, n_images, channels, h,
                            w, stream);
 }
 
@@ -567,7 +572,7 @@ extern "C" int ppo_impala_stack_tail_backward_bf16x3(const float *g, const void 
                                                      float *g1, float *da0, float *g0, int n_images, int channels, int h, int w,
                                                      void *stream)
 {
-    return ppo::split_tail("ppo_impala_stack_tail_backward_bf16x3", true, g, packed_t, masks, da1, g1, da0, g0, n_images, channels,
+    return ppo::split_tail<true>("ppo_impala_stack_tail_backward_bf16x3", g, packed_t, masks, da1, g1, da0, g0, n_images, channels,
                            h, w, stream);
 }
 
@@ -581,7 +586,7 @@ extern "C" int ppo_impala_stack_tail_forward_signs_bf16x3(const float *in, const
                                                           int channels, int h, int w, void *stream)
 {
     if (!signs) return ppo::fail(PPO_E_INVALID, "ppo_impala_stack_tail_forward_signs_bf16x3: null sign table");
-    return ppo::split_tail("ppo_impala_stack_tail_forward_signs_bf16x3", false, in, packed, biases, a0, q0, a1, q1, n_images, channels,
+    return ppo::split_tail<false>("ppo_impala_stack_tail_forward_signs_bf16x3", in, packed, biases, a0, q0, a1, q1, n_images, channels,
                            h, w, stream, signs);
 }
 
@@ -590,6 +595,6 @@ extern "C" int ppo_impala_stack_tail_backward_signs_bf16x3(const float *g, const
                                                            void *stream)
 {
     if (!signs) return ppo::fail(PPO_E_INVALID, "ppo_impala_stack_tail_backward_signs_bf16x3: null sign table");
-    return ppo::split_tail("ppo_impala_stack_tail_backward_signs_bf16x3", true, g, packed_t, nullptr, da1, g1, da0, g0, n_images,
+    return ppo::split_tail<true>("ppo_impala_stack_tail_backward_signs_bf16x3", g, packed_t, nullptr, da1, g1, da0, g0, n_images,
                            channels, h, w, stream, const_cast<uint8_t *const *>(signs));
 }

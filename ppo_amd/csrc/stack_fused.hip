@@ -989,7 +989,7 @@ __global__ __launch_bounds__(NW * NSPLIT * 64) void stack_full_bwd_kernel(StackF
 }
 
 template <int C, int HI, int WI, int MTI, int HO, int WO, int MTO, int NW, int NSPLIT>
-int launch_stack_full_bwd(const StackFullBwdArgs &args, hipStream_t st)
+int launch_stack_full(const StackFullBwdArgs &args, hipStream_t st)  // the argument struct picks forward or backward
 {
     using SI = StackCfg<C, HI, WI, MTI, NW, NSPLIT, WI + 1>;  // the kernel's own padded layout
     constexpr size_t kLds = 2 * (size_t)SI::LDS_MAP * 4;
@@ -1192,14 +1192,133 @@ int launch_chain_split(const ChainSplitArgs &args, hipStream_t st)
     return check_launch("stack_chain_split_kernel");
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// The host side of the entry points.  A kernel family's geometries stand in ONE case list, its dispatcher.  Called
+// without arguments (args == nullptr) a dispatcher launches nothing and answers PPO_OK / PPO_E_INVALID: that is what the
+// *_supported probes are, so "supported" and "has a kernel" cannot drift apart.
+#define PPO_STACK_CASE(LAUNCH, C, H, W, ...) \
+    if (channels == C && h == H && w == W) return args ? LAUNCH<C, H, W, __VA_ARGS__>(*args, st) : PPO_OK;
+
+int no_kernel(const char *who, int channels, int h, int w)
+{
+    return fail(PPO_E_INVALID, "%s: no kernel for %d channels at %dx%d", who, channels, h, w);
+}
+
+// The residual blocks of one stack.  84x84 observations: 42x42, 21x21 and 11x11 maps; 64x64 (procgen): 32x32, 16x16 and 8x8.
+// 16 channels: the in-place shifted form (stack_shift_kernel; TR); 32 channels: stack_tail_kernel (MT, NW, NSPLIT)
+template <bool BACKWARD>
+int dispatch_stack_tail(const char *who, int channels, int h, int w, const StackTailArgs *args, hipStream_t st)
+{
+    PPO_STACK_CASE(launch_stack_shift, 16, 42, 42, 6, BACKWARD)
+    PPO_STACK_CASE(launch_stack_shift, 16, 32, 32, 8, BACKWARD)
+    PPO_STACK_CASE(launch_stack_tail, 32, 11, 11, 2, 4, PPO_TAIL_SPLIT, BACKWARD)
+    PPO_STACK_CASE(launch_stack_tail, 32, 21, 21, 7, 4, PPO_TAIL_SPLIT, BACKWARD)
+    PPO_STACK_CASE(launch_stack_tail, 32, 16, 16, 4, 4, PPO_TAIL_SPLIT, BACKWARD)
+    PPO_STACK_CASE(launch_stack_tail, 32, 8, 8, 1, 4, PPO_TAIL_SPLIT, BACKWARD)
+    return args ? no_kernel(who, channels, h, w) : PPO_E_INVALID;
+}
+
+// A whole stack, alone or chained to its neighbour, forward (StackFullArgs) or backward (StackFullBwdArgs):
+// (C, HI, WI, MTI, HO, WO, MTO, NW, NSPLIT)
+template <class Args>
+int dispatch_stack_full(const char *who, int channels, int h, int w, const Args *args, hipStream_t st)
+{
+    PPO_STACK_CASE(launch_stack_full, 32, 21, 21, 7, 11, 11, 2, 4, 2)
+    PPO_STACK_CASE(launch_stack_full, 32, 16, 16, 4, 8, 8, 1, 4, 2)
+    return args ? no_kernel(who, channels, h, w) : PPO_E_INVALID;
+}
+
+int dispatch_chain_split(const char *who, int channels, int h, int w, const ChainSplitArgs *args, hipStream_t st)
+{
+    PPO_STACK_CASE(launch_chain_split, 32, 21, 21, 11, 11)
+    return args ? no_kernel(who, channels, h, w) : PPO_E_INVALID;
+}
+#undef PPO_STACK_CASE
+
+// One layer table of the entry point `who`: N packed-weight pointers, 16-byte aligned, and the first M pointers of their
+// companion table (`other`: "bias" or "mask"), none of them null, copied into the launch arguments.
+template <int N, int M>
+int fill_layers(const char *who, const char *other, const float *const *weights, const float *const *others,
+                const float *(&w)[N], const float *(&o)[M])
+{
+    for (int l = 0; l < N; ++l) {
+        if (!weights[l] || (l < M && !others[l])) return fail(PPO_E_INVALID, "%s: null weights / %s of layer %d", who, other, l);
+        if (!aligned(weights[l], 16)) return fail(PPO_E_ALIGN, "%s: packed weights must be 16-byte aligned", who);
+        w[l] = weights[l];
+        if (l < M) o[l] = others[l];
+    }
+    return PPO_OK;
+}
+
+// The neighbouring stack of a chained launch: its two layer tables (weights; biases forward, masks backward) and its
+// four maps.  Absent (nullptr) in the plain ppo_impala_stack_full_* calls.
+struct ChainedStack {
+    const float *const *weights, *const *others;
+    float *save[4];
+};
+
+// ppo_impala_stack_full_forward_f32 (pre == nullptr) and ppo_impala_stack_chain_forward_f32
+int stack_full_forward(const char *who, const float *in, const ChainedStack *pre, const float *const *packed_weights,
+                       const float *const *biases, float *pooled, uint8_t *argmax, float *a0, float *q0, float *a1, float *q1,
+                       int n_images, int channels, int h, int w, void *stream)
+{
+    if (n_images < 0) return fail(PPO_E_INVALID, "%s: negative batch", who);
+    if (n_images == 0) return PPO_OK;
+    if (!in || !packed_weights || !biases || !q1 || (pre && (!pre->weights || !pre->others)))
+        return fail(PPO_E_INVALID, "%s: null pointer", who);
+    StackFullArgs args{};
+    args.in = in, args.pooled = pooled, args.argmax = argmax, args.n_images = n_images;
+    args.save[0] = a0, args.save[1] = q0, args.save[2] = a1, args.save[3] = q1;
+    if (int rc = fill_layers(who, "bias", packed_weights, biases, args.w, args.bias)) return rc;
+    if (pre) {
+        if (int rc = fill_layers(who, "bias", pre->weights, pre->others, args.pre_w, args.pre_bias)) return rc;
+        for (int l = 0; l < 4; ++l) args.pre_save[l] = pre->save[l];
+        args.has_pre = 1;
+    }
+    return dispatch_stack_full(who, channels, h, w, &args, as_stream(stream));
+}
+
+// ppo_impala_stack_full_backward_f32 (post == nullptr) and ppo_impala_stack_chain_backward_f32
+int stack_full_backward(const char *who, const float *g, const float *const *packed_weights_t, const float *const *masks,
+                        const uint8_t *argmax, float *da1, float *g1, float *da0, float *g0, float *dc, float *g_prev,
+                        const ChainedStack *post, int n_images, int channels, int h, int w, void *stream)
+{
+    if (n_images < 0) return fail(PPO_E_INVALID, "%s: negative batch", who);
+    if (n_images == 0) return PPO_OK;
+    if (!g || !packed_weights_t || !masks || !argmax || !da1 || !g1 || !da0 || !g0 || !dc || !g_prev ||
+        (post && (!post->weights || !post->others || !post->save[0] || !post->save[1] || !post->save[2] || !post->save[3])))
+        return fail(PPO_E_INVALID, "%s: null pointer", who);
+    if (!aligned(argmax, 4)) return fail(PPO_E_ALIGN, "%s: argmax must be 4-byte aligned", who);
+    StackFullBwdArgs args{};
+    args.g = g, args.argmax = argmax, args.dc = dc, args.g_prev = g_prev, args.n_images = n_images;
+    args.save[0] = da1, args.save[1] = g1, args.save[2] = da0, args.save[3] = g0;
+    if (int rc = fill_layers(who, "mask", packed_weights_t, masks, args.w, args.mask)) return rc;
+    if (post) {
+        if (int rc = fill_layers(who, "mask", post->weights, post->others, args.post_w, args.post_mask)) return rc;
+        for (int l = 0; l < 4; ++l) args.post_save[l] = post->save[l];
+        args.has_post = 1;
+    }
+    return dispatch_stack_full(who, channels, h, w, &args, as_stream(stream));
+}
+
+// The chain-split workspace: exchange slots [n][2][C][h*w] floats, then flags [n][2], then control words [4] (all
+// 16-byte aligned inside the block)
+struct ChainSplitLayout {
+    size_t flags, ctl, bytes;  // byte offsets of the flags and of the control words, size of the whole
+};
+ChainSplitLayout chain_split_layout(int n_images, int channels, int h, int w)
+{
+    const size_t slots = (size_t)n_images * 2 * channels * h * w * sizeof(float);
+    const size_t flags = ((size_t)n_images * 2 * sizeof(uint32_t) + 15) & ~(size_t)15;
+    return {slots, slots + flags, slots + flags + 16};
+}
+
 }  // namespace
 }  // namespace ppo
 
 extern "C" int ppo_impala_stack_tail_supported(int channels, int h, int w)
 {
-    // 84x84 observations: 21x21 and 11x11; 64x64 (procgen): 16x16 and 8x8
-    if (channels == 16) return (h == 42 && w == 42) || (h == 32 && w == 32);  // in-place shifted form (stack_shift_kernel)
-    return channels == 32 && ((h == 11 && w == 11) || (h == 21 && w == 21) || (h == 16 && w == 16) || (h == 8 && w == 8));
+    return ppo::dispatch_stack_tail<false>(nullptr, channels, h, w, nullptr, nullptr) == PPO_OK;
 }
 
 extern "C" int ppo_impala_stack_tail_forward_f32(const float *in, const float *const *packed_weights,
@@ -1207,41 +1326,22 @@ extern "C" int ppo_impala_stack_tail_forward_f32(const float *in, const float *c
                                                  int n_images, int channels, int h, int w, void *stream)
 {
     using namespace ppo;
-    if (n_images < 0) return fail(PPO_E_INVALID, "ppo_impala_stack_tail_forward_f32: negative batch");
+    const char *who = "ppo_impala_stack_tail_forward_f32";
+    if (n_images < 0) return fail(PPO_E_INVALID, "%s: negative batch", who);
     if (n_images == 0) return PPO_OK;
-    if (!in || !packed_weights || !biases || !q1)
-        return fail(PPO_E_INVALID, "ppo_impala_stack_tail_forward_f32: null pointer");
-    StackTailArgs args;
-    args.in = in;
-    for (int l = 0; l < 4; ++l) {
-        if (!packed_weights[l] || !biases[l])
-            return fail(PPO_E_INVALID, "ppo_impala_stack_tail_forward_f32: null weights / bias of layer %d", l);
-        if (!aligned(packed_weights[l], 16))
-            return fail(PPO_E_ALIGN, "ppo_impala_stack_tail_forward_f32: packed weights must be 16-byte aligned");
-        args.w[l] = packed_weights[l];
-        args.bias[l] = biases[l];
-        args.mask[l] = nullptr;
-    }
-    if (!aligned(in, 4)) return fail(PPO_E_ALIGN, "ppo_impala_stack_tail_forward_f32: input must be 4-byte aligned");
-    args.save[0] = a0;
-    args.save[1] = q0;
-    args.save[2] = a1;
-    args.save[3] = q1;
-    args.n_images = n_images;
-    hipStream_t st = as_stream(stream);
+    if (!in || !packed_weights || !biases || !q1) return fail(PPO_E_INVALID, "%s: null pointer", who);
+    StackTailArgs args{};
+    args.in = in, args.n_images = n_images;
+    args.save[0] = a0, args.save[1] = q0, args.save[2] = a1, args.save[3] = q1;
+    if (int rc = fill_layers(who, "bias", packed_weights, biases, args.w, args.bias)) return rc;
+    if (!aligned(in, 4)) return fail(PPO_E_ALIGN, "%s: input must be 4-byte aligned", who);
     if (channels == 16) {
         // the skip connection of the second block is re-read from q0, so q0 is required even when nothing else is kept
-        if (!q0) return fail(PPO_E_INVALID, "ppo_impala_stack_tail_forward_f32: the 16-channel form needs q0 (its second block re-reads it)");
+        if (!q0) return fail(PPO_E_INVALID, "%s: the 16-channel form needs q0 (its second block re-reads it)", who);
         if (!aligned(in, 16) || !aligned(q0, 16) || !aligned(q1, 16) || (a0 && !aligned(a0, 16)) || (a1 && !aligned(a1, 16)))
-            return fail(PPO_E_ALIGN, "ppo_impala_stack_tail_forward_f32: the 16-channel form needs 16-byte aligned maps");
-        if (h == 42 && w == 42) return launch_stack_shift<16, 42, 42, 6, false>(args, st);
-        if (h == 32 && w == 32) return launch_stack_shift<16, 32, 32, 8, false>(args, st);
+            return fail(PPO_E_ALIGN, "%s: the 16-channel form needs 16-byte aligned maps", who);
     }
-    if (channels == 32 && h == 11 && w == 11) return launch_stack_tail<32, 11, 11, 2, 4, PPO_TAIL_SPLIT, false>(args, st);
-    if (channels == 32 && h == 21 && w == 21) return launch_stack_tail<32, 21, 21, 7, 4, PPO_TAIL_SPLIT, false>(args, st);
-    if (channels == 32 && h == 16 && w == 16) return launch_stack_tail<32, 16, 16, 4, 4, PPO_TAIL_SPLIT, false>(args, st);
-    if (channels == 32 && h == 8 && w == 8) return launch_stack_tail<32, 8, 8, 1, 4, PPO_TAIL_SPLIT, false>(args, st);
-    return fail(PPO_E_INVALID, "ppo_impala_stack_tail_forward_f32: no kernel for %d channels at %dx%d", channels, h, w);
+    return dispatch_stack_tail<false>(who, channels, h, w, &args, as_stream(stream));
 }
 
 extern "C" int ppo_impala_stack_tail_backward_f32(const float *g, const float *const *packed_weights_t,
@@ -1249,45 +1349,24 @@ extern "C" int ppo_impala_stack_tail_backward_f32(const float *g, const float *c
                                                   int n_images, int channels, int h, int w, void *stream)
 {
     using namespace ppo;
-    if (n_images < 0) return fail(PPO_E_INVALID, "ppo_impala_stack_tail_backward_f32: negative batch");
+    const char *who = "ppo_impala_stack_tail_backward_f32";
+    if (n_images < 0) return fail(PPO_E_INVALID, "%s: negative batch", who);
     if (n_images == 0) return PPO_OK;
-    if (!g || !packed_weights_t || !masks || !da1 || !g1 || !da0 || !g0)
-        return fail(PPO_E_INVALID, "ppo_impala_stack_tail_backward_f32: null pointer");
-    StackTailArgs args;
-    args.in = g;
-    for (int l = 0; l < 4; ++l) {
-        if (!packed_weights_t[l] || !masks[l])
-            return fail(PPO_E_INVALID, "ppo_impala_stack_tail_backward_f32: null weights / mask of layer %d", l);
-        if (!aligned(packed_weights_t[l], 16))
-            return fail(PPO_E_ALIGN, "ppo_impala_stack_tail_backward_f32: packed weights must be 16-byte aligned");
-        args.w[l] = packed_weights_t[l];
-        args.bias[l] = nullptr;
-        args.mask[l] = masks[l];
-    }
-    args.save[0] = da1;
-    args.save[1] = g1;
-    args.save[2] = da0;
-    args.save[3] = g0;
-    args.n_images = n_images;
-    hipStream_t st = as_stream(stream);
-    if (channels == 16) {
+    if (!g || !packed_weights_t || !masks || !da1 || !g1 || !da0 || !g0) return fail(PPO_E_INVALID, "%s: null pointer", who);
+    StackTailArgs args{};
+    args.in = g, args.n_images = n_images;
+    args.save[0] = da1, args.save[1] = g1, args.save[2] = da0, args.save[3] = g0;
+    if (int rc = fill_layers(who, "mask", packed_weights_t, masks, args.w, args.mask)) return rc;
+    if (channels == 16)
         for (const void *ptr : {(const void *)g, (const void *)da1, (const void *)g1, (const void *)da0, (const void *)g0,
                                 (const void *)masks[0], (const void *)masks[1], (const void *)masks[2], (const void *)masks[3]})
-            if (!aligned(ptr, 16))
-                return fail(PPO_E_ALIGN, "ppo_impala_stack_tail_backward_f32: the 16-channel form needs 16-byte aligned maps");
-        if (h == 42 && w == 42) return launch_stack_shift<16, 42, 42, 6, true>(args, st);
-        if (h == 32 && w == 32) return launch_stack_shift<16, 32, 32, 8, true>(args, st);
-    }
-    if (channels == 32 && h == 11 && w == 11) return launch_stack_tail<32, 11, 11, 2, 4, PPO_TAIL_SPLIT, true>(args, st);
-    if (channels == 32 && h == 21 && w == 21) return launch_stack_tail<32, 21, 21, 7, 4, PPO_TAIL_SPLIT, true>(args, st);
-    if (channels == 32 && h == 16 && w == 16) return launch_stack_tail<32, 16, 16, 4, 4, PPO_TAIL_SPLIT, true>(args, st);
-    if (channels == 32 && h == 8 && w == 8) return launch_stack_tail<32, 8, 8, 1, 4, PPO_TAIL_SPLIT, true>(args, st);
-    return fail(PPO_E_INVALID, "ppo_impala_stack_tail_backward_f32: no kernel for %d channels at %dx%d", channels, h, w);
+            if (!aligned(ptr, 16)) return fail(PPO_E_ALIGN, "%s: the 16-channel form needs 16-byte aligned maps", who);
+    return dispatch_stack_tail<true>(who, channels, h, w, &args, as_stream(stream));
 }
 
 extern "C" int ppo_impala_stack_full_supported(int channels, int h, int w)
 {
-    return channels == 32 && ((h == 21 && w == 21) || (h == 16 && w == 16));
+    return ppo::dispatch_stack_full<ppo::StackFullArgs>(nullptr, channels, h, w, nullptr, nullptr) == PPO_OK;
 }
 
 extern "C" int ppo_impala_stack_full_forward_f32(const float *in, const float *const *packed_weights,
@@ -1295,39 +1374,8 @@ extern "C" int ppo_impala_stack_full_forward_f32(const float *in, const float *c
                                                  float *q0, float *a1, float *q1, int n_images, int channels, int h, int w,
                                                  void *stream)
 {
-    using namespace ppo;
-    if (n_images < 0) return fail(PPO_E_INVALID, "ppo_impala_stack_full_forward_f32: negative batch");
-    if (n_images == 0) return PPO_OK;
-    if (!in || !packed_weights || !biases || !q1)
-        return fail(PPO_E_INVALID, "ppo_impala_stack_full_forward_f32: null pointer");
-    StackFullArgs args;
-    args.in = in;
-    for (int l = 0; l < 5; ++l) {
-        if (!packed_weights[l] || !biases[l])
-            return fail(PPO_E_INVALID, "ppo_impala_stack_full_forward_f32: null weights / bias of layer %d", l);
-        if (!aligned(packed_weights[l], 16))
-            return fail(PPO_E_ALIGN, "ppo_impala_stack_full_forward_f32: packed weights must be 16-byte aligned");
-        args.w[l] = packed_weights[l];
-        args.bias[l] = biases[l];
-    }
-    args.pooled = pooled;
-    args.argmax = argmax;
-    args.save[0] = a0;
-    args.save[1] = q0;
-    args.save[2] = a1;
-    args.save[3] = q1;
-    args.has_pre = 0;
-    for (int l = 0; l < 4; ++l) {
-        args.pre_w[l] = nullptr;
-        args.pre_bias[l] = nullptr;
-        args.pre_save[l] = nullptr;
-    }
-    args.n_images = n_images;
-    if (channels == 32 && h == 21 && w == 21)
-        return launch_stack_full<32, 21, 21, 7, 11, 11, 2, 4, 2>(args, as_stream(stream));
-    if (channels == 32 && h == 16 && w == 16)
-        return launch_stack_full<32, 16, 16, 4, 8, 8, 1, 4, 2>(args, as_stream(stream));
-    return fail(PPO_E_INVALID, "ppo_impala_stack_full_forward_f32: no kernel for %d channels at %dx%d", channels, h, w);
+    return ppo::stack_full_forward("ppo_impala_stack_full_forward_f32", in, nullptr, packed_weights, biases, pooled, argmax, a0,
+                                   q0, a1, q1, n_images, channels, h, w, stream);
 }
 
 extern "C" int ppo_impala_stack_chain_forward_f32(const float *in, const float *const *pre_packed_weights,
@@ -1337,42 +1385,9 @@ extern "C" int ppo_impala_stack_chain_forward_f32(const float *in, const float *
                                                   float *q0, float *a1, float *q1, int n_images, int channels, int h, int w,
                                                   void *stream)
 {
-    using namespace ppo;
-    if (n_images < 0) return fail(PPO_E_INVALID, "ppo_impala_stack_chain_forward_f32: negative batch");
-    if (n_images == 0) return PPO_OK;
-    if (!in || !pre_packed_weights || !pre_biases || !packed_weights || !biases || !q1)
-        return fail(PPO_E_INVALID, "ppo_impala_stack_chain_forward_f32: null pointer");
-    StackFullArgs args;
-    args.in = in;
-    for (int l = 0; l < 5; ++l) {
-        if (!packed_weights[l] || !biases[l] || (l < 4 && (!pre_packed_weights[l] || !pre_biases[l])))
-            return fail(PPO_E_INVALID, "ppo_impala_stack_chain_forward_f32: null weights / bias of layer %d", l);
-        if (!aligned(packed_weights[l], 16) || (l < 4 && !aligned(pre_packed_weights[l], 16)))
-            return fail(PPO_E_ALIGN, "ppo_impala_stack_chain_forward_f32: packed weights must be 16-byte aligned");
-        args.w[l] = packed_weights[l];
-        args.bias[l] = biases[l];
-        if (l < 4) {
-            args.pre_w[l] = pre_packed_weights[l];
-            args.pre_bias[l] = pre_biases[l];
-        }
-    }
-    args.pre_save[0] = pre_a0;
-    args.pre_save[1] = pre_q0;
-    args.pre_save[2] = pre_a1;
-    args.pre_save[3] = pre_q1;
-    args.has_pre = 1;
-    args.pooled = pooled;
-    args.argmax = argmax;
-    args.save[0] = a0;
-    args.save[1] = q0;
-    args.save[2] = a1;
-    args.save[3] = q1;
-    args.n_images = n_images;
-    if (channels == 32 && h == 21 && w == 21)
-        return launch_stack_full<32, 21, 21, 7, 11, 11, 2, 4, 2>(args, as_stream(stream));
-    if (channels == 32 && h == 16 && w == 16)
-        return launch_stack_full<32, 16, 16, 4, 8, 8, 1, 4, 2>(args, as_stream(stream));
-    return fail(PPO_E_INVALID, "ppo_impala_stack_chain_forward_f32: no kernel for %d channels at %dx%d", channels, h, w);
+    const ppo::ChainedStack pre{pre_packed_weights, pre_biases, {pre_a0, pre_q0, pre_a1, pre_q1}};
+    return ppo::stack_full_forward("ppo_impala_stack_chain_forward_f32", in, &pre, packed_weights, biases, pooled, argmax, a0,
+                                   q0, a1, q1, n_images, channels, h, w, stream);
 }
 
 extern "C" int ppo_impala_stack_full_backward_f32(const float *g, const float *const *packed_weights_t,
@@ -1380,41 +1395,8 @@ extern "C" int ppo_impala_stack_full_backward_f32(const float *g, const float *c
                                                   float *da0, float *g0, float *dc, float *g_prev, int n_images,
                                                   int channels, int h, int w, void *stream)
 {
-    using namespace ppo;
-    if (n_images < 0) return fail(PPO_E_INVALID, "ppo_impala_stack_full_backward_f32: negative batch");
-    if (n_images == 0) return PPO_OK;
-    if (!g || !packed_weights_t || !masks || !argmax || !da1 || !g1 || !da0 || !g0 || !dc || !g_prev)
-        return fail(PPO_E_INVALID, "ppo_impala_stack_full_backward_f32: null pointer");
-    if (!aligned(argmax, 4)) return fail(PPO_E_ALIGN, "ppo_impala_stack_full_backward_f32: argmax must be 4-byte aligned");
-    StackFullBwdArgs args;
-    args.g = g;
-    for (int l = 0; l < 5; ++l) {
-        if (!packed_weights_t[l] || (l < 4 && !masks[l]))
-            return fail(PPO_E_INVALID, "ppo_impala_stack_full_backward_f32: null weights / mask of layer %d", l);
-        if (!aligned(packed_weights_t[l], 16))
-            return fail(PPO_E_ALIGN, "ppo_impala_stack_full_backward_f32: packed weights must be 16-byte aligned");
-        args.w[l] = packed_weights_t[l];
-        if (l < 4) args.mask[l] = masks[l];
-    }
-    args.argmax = argmax;
-    args.save[0] = da1;
-    args.save[1] = g1;
-    args.save[2] = da0;
-    args.save[3] = g0;
-    args.dc = dc;
-    args.g_prev = g_prev;
-    for (int l = 0; l < 4; ++l) {
-        args.post_w[l] = nullptr;
-        args.post_mask[l] = nullptr;
-        args.post_save[l] = nullptr;
-    }
-    args.has_post = 0;
-    args.n_images = n_images;
-    if (channels == 32 && h == 21 && w == 21)
-        return launch_stack_full_bwd<32, 21, 21, 7, 11, 11, 2, 4, 2>(args, as_stream(stream));
-    if (channels == 32 && h == 16 && w == 16)
-        return launch_stack_full_bwd<32, 16, 16, 4, 8, 8, 1, 4, 2>(args, as_stream(stream));
-    return fail(PPO_E_INVALID, "ppo_impala_stack_full_backward_f32: no kernel for %d channels at %dx%d", channels, h, w);
+    return ppo::stack_full_backward("ppo_impala_stack_full_backward_f32", g, packed_weights_t, masks, argmax, da1, g1, da0, g0,
+                                    dc, g_prev, nullptr, n_images, channels, h, w, stream);
 }
 
 extern "C" int ppo_impala_stack_chain_backward_f32(const float *g, const float *const *packed_weights_t,
@@ -1424,53 +1406,14 @@ extern "C" int ppo_impala_stack_chain_backward_f32(const float *g, const float *
                                                    float *post_da1, float *post_g1, float *post_da0, float *post_g0,
                                                    int n_images, int channels, int h, int w, void *stream)
 {
-    using namespace ppo;
-    if (n_images < 0) return fail(PPO_E_INVALID, "ppo_impala_stack_chain_backward_f32: negative batch");
-    if (n_images == 0) return PPO_OK;
-    if (!g || !packed_weights_t || !masks || !argmax || !da1 || !g1 || !da0 || !g0 || !dc || !g_prev || !post_packed_weights_t
-        || !post_masks || !post_da1 || !post_g1 || !post_da0 || !post_g0)
-        return fail(PPO_E_INVALID, "ppo_impala_stack_chain_backward_f32: null pointer");
-    if (!aligned(argmax, 4)) return fail(PPO_E_ALIGN, "ppo_impala_stack_chain_backward_f32: argmax must be 4-byte aligned");
-    StackFullBwdArgs args;
-    args.g = g;
-    for (int l = 0; l < 5; ++l) {
-        if (!packed_weights_t[l] || (l < 4 && (!masks[l] || !post_packed_weights_t[l] || !post_masks[l])))
-            return fail(PPO_E_INVALID, "ppo_impala_stack_chain_backward_f32: null weights / mask of layer %d", l);
-        if (!aligned(packed_weights_t[l], 16) || (l < 4 && !aligned(post_packed_weights_t[l], 16)))
-            return fail(PPO_E_ALIGN, "ppo_impala_stack_chain_backward_f32: packed weights must be 16-byte aligned");
-        args.w[l] = packed_weights_t[l];
-        if (l < 4) {
-            args.mask[l] = masks[l];
-            args.post_w[l] = post_packed_weights_t[l];
-            args.post_mask[l] = post_masks[l];
-        }
-    }
-    args.argmax = argmax;
-    args.save[0] = da1;
-    args.save[1] = g1;
-    args.save[2] = da0;
-    args.save[3] = g0;
-    args.dc = dc;
-    args.g_prev = g_prev;
-    args.post_save[0] = post_da1;
-    args.post_save[1] = post_g1;
-    args.post_save[2] = post_da0;
-    args.post_save[3] = post_g0;
-    args.has_post = 1;
-    args.n_images = n_images;
-    if (channels == 32 && h == 21 && w == 21)
-        return launch_stack_full_bwd<32, 21, 21, 7, 11, 11, 2, 4, 2>(args, as_stream(stream));
-    if (channels == 32 && h == 16 && w == 16)
-        return launch_stack_full_bwd<32, 16, 16, 4, 8, 8, 1, 4, 2>(args, as_stream(stream));
-    return fail(PPO_E_INVALID, "ppo_impala_stack_chain_backward_f32: no kernel for %d channels at %dx%d", channels, h, w);
+    const ppo::ChainedStack post{post_packed_weights_t, post_masks, {post_da1, post_g1, post_da0, post_g0}};
+    return ppo::stack_full_backward("ppo_impala_stack_chain_backward_f32", g, packed_weights_t, masks, argmax, da1, g1, da0, g0,
+                                    dc, g_prev, &post, n_images, channels, h, w, stream);
 }
 
 extern "C" size_t ppo_impala_stack_chain_split_workspace_bytes(int n_images, int channels, int h, int w)
 {
-    // exchange slots [n][2][C][h*w] floats, flags [n][2], control words [4] (all 16-byte aligned inside the block)
-    const size_t slots = (size_t)n_images * 2 * channels * h * w * sizeof(float);
-    const size_t flags = ((size_t)n_images * 2 * sizeof(uint32_t) + 15) & ~(size_t)15;
-    return slots + flags + 16;
+    return ppo::chain_split_layout(n_images, channels, h, w).bytes;
 }
 
 extern "C" int ppo_impala_stack_chain_split_forward_f32(const float *in, const float *const *pre_packed_weights,
@@ -1480,40 +1423,26 @@ extern "C" int ppo_impala_stack_chain_split_forward_f32(const float *in, const f
                                                         int channels, int h, int w, void *stream)
 {
     using namespace ppo;
-    if (n_images < 0) return fail(PPO_E_INVALID, "ppo_impala_stack_chain_split_forward_f32: negative batch");
+    const char *who = "ppo_impala_stack_chain_split_forward_f32";
+    if (n_images < 0) return fail(PPO_E_INVALID, "%s: negative batch", who);
     if (n_images == 0) return PPO_OK;
     if (!in || !pre_packed_weights || !pre_biases || !packed_weights || !biases || !q1 || !workspace)
-        return fail(PPO_E_INVALID, "ppo_impala_stack_chain_split_forward_f32: null pointer");
-    if (!(channels == 32 && h == 21 && w == 21))
-        return fail(PPO_E_INVALID, "ppo_impala_stack_chain_split_forward_f32: no kernel for %d channels at %dx%d", channels, h, w);
-    if (workspace_bytes < ppo_impala_stack_chain_split_workspace_bytes(n_images, channels, h, w) || !aligned(workspace, 16))
-        return fail(PPO_E_INVALID, "ppo_impala_stack_chain_split_forward_f32: workspace too small or misaligned");
-    ChainSplitArgs args;
-    args.in = in;
-    for (int l = 0; l < 5; ++l) {
-        if (!packed_weights[l] || !biases[l] || (l < 4 && (!pre_packed_weights[l] || !pre_biases[l])))
-            return fail(PPO_E_INVALID, "ppo_impala_stack_chain_split_forward_f32: null weights / bias of layer %d", l);
-        if (!aligned(packed_weights[l], 16) || (l < 4 && !aligned(pre_packed_weights[l], 16)))
-            return fail(PPO_E_ALIGN, "ppo_impala_stack_chain_split_forward_f32: packed weights must be 16-byte aligned");
-        args.w[l] = packed_weights[l];
-        args.bias[l] = biases[l];
-        if (l < 4) {
-            args.pre_w[l] = pre_packed_weights[l];
-            args.pre_bias[l] = pre_biases[l];
-        }
-    }
-    args.out = q1;
-    const size_t slots = (size_t)n_images * 2 * channels * h * w * sizeof(float);
-    const size_t flags = ((size_t)n_images * 2 * sizeof(uint32_t) + 15) & ~(size_t)15;
+        return fail(PPO_E_INVALID, "%s: null pointer", who);
+    // the geometry comes before the workspace, whose size depends on it: ask the case list first (a probe says nothing, so
+    // the text is made here; the dispatch at the end cannot fail on the geometry any more)
+    if (dispatch_chain_split(who, channels, h, w, nullptr, nullptr) != PPO_OK) return no_kernel(who, channels, h, w);
+    const ChainSplitLayout at = chain_split_layout(n_images, channels, h, w);
+    if (workspace_bytes < at.bytes || !aligned(workspace, 16)) return fail(PPO_E_INVALID, "%s: workspace too small or misaligned", who);
+    ChainSplitArgs args{};
+    args.in = in, args.out = q1, args.n_images = n_images;
+    if (int rc = fill_layers(who, "bias", packed_weights, biases, args.w, args.bias)) return rc;
+    if (int rc = fill_layers(who, "bias", pre_packed_weights, pre_biases, args.pre_w, args.pre_bias)) return rc;
     args.xbuf = static_cast<float *>(workspace);
-    args.flags = reinterpret_cast<uint32_t *>(static_cast<char *>(workspace) + slots);
-    args.ctl = reinterpret_cast<uint32_t *>(static_cast<char *>(workspace) + slots + flags);
-    args.n_images = n_images;
+    args.flags = reinterpret_cast<uint32_t *>(static_cast<char *>(workspace) + at.flags);
+    args.ctl = reinterpret_cast<uint32_t *>(static_cast<char *>(workspace) + at.ctl);
 #ifdef PPO_TUNE_TIMING_AIDS  // tools/build_variant.sh builds only: the shipped library has no switch that voids results
     static const int skip = getenv("PPO_AMD_SPLIT_SKIP") ? atoi(getenv("PPO_AMD_SPLIT_SKIP")) : 0;
     args.skip = skip;
-#else
-    args.skip = 0;
 #endif
-    return launch_chain_split<32, 21, 21, 11, 11>(args, as_stream(stream));
+    return dispatch_chain_split(who, channels, h, w, &args, as_stream(stream));
 }

@@ -9,7 +9,8 @@
 tree.  `compare` cuts each listing into one piece per function symbol - its preamble, its code, a kernel's
 .amdhsa_kernel descriptor block and the resource summary that follows - and pairs the pieces of A and B by symbol, so
 the order in which the compiler emitted them does not matter; the labels that carry a function's ordinal (.LBB<n>_<m>,
-.Lfunc_end<n>, .LJTI<n>_<m>, BB<n>_<m> in comments) are written without it.  Each kernel's entry under amdhsa.kernels is
+.Lfunc_end<n>, .LJTI<n>_<m>, BB<n>_<m> in comments) are written without it, and the blanks that align the comment behind
+a block label (as many as the ordinal's digits leave room for) as one.  Each kernel's entry under amdhsa.kernels is
 compared with its piece, and what is left of the file (object definitions, section bookkeeping, the rest of the metadata)
 as a sorted list of lines.  Only the lines that name the per-compilation `__hip_cuid_<hash>` symbol are left out.  The tool compares
 text: it does not look for anything in a listing.  It prints `equal: N files, M kernels`, or the first differing symbol
@@ -25,6 +26,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 ARCH = "gfx950"
 ORDINAL = re.compile(r"(\.LBB|\.Lfunc_begin|\.Lfunc_end|\.LJTI|\bBB)\d+")  # BB<n>_<m>: the loop comments
+LABEL_PAD = re.compile(r"^(\.LBB_\d+:)\s+;")  # the comment behind a block label is aligned by the label's width
 BEGIN = re.compile(r"; -- Begin function (\S+)")
 RESOURCE = re.compile(r"\t\.set |\t\.section\t\.AMDGPU\.csdata|;")  # what follows a function's end and belongs to it
 
@@ -53,7 +55,7 @@ def record(root, out):
 def split(path):
     """-> ({symbol: lines}, sorted rest, kernel count)"""
     with open(path) as f:
-        lines = [ORDINAL.sub(r"\1", l.rstrip()) for l in f if "__hip_cuid_" not in l]
+        lines = [LABEL_PAD.sub(r"\1 ;", ORDINAL.sub(r"\1", l.rstrip())) for l in f if "__hip_cuid_" not in l]
     meta_at = next((i for i, l in enumerate(lines) if l.strip() == ".amdgpu_metadata"), len(lines))
     pieces, rest = {}, []
     begins = [i for i in range(meta_at) if BEGIN.search(lines[i])]
