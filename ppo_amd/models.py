@@ -72,9 +72,9 @@ FUSE_STACK_CHAIN = int(os.environ.get("PPO_AMD_FUSE_STACK_CHAIN", "1"))
 # the CU time: variants alternated rollout by rollout in one process (tools/rollout_ab.py; separate processes differ by
 # more than the effect) 0.4846 -> 0.4649 ms per env step, 0.4584 with the action step inside the heads launch as well.
 # A partner that never arrives sets an error word which the Runner checks after every rollout (chain_split_error) and
-# answers by dropping to the one-workgroup launch and redoing the rollout (Runner.generate_rollout).  Only a forward made
-# under `net.allow_chain_split` (the Runner's pipelined rollout sets it, and checks) takes the split launch: evaluation,
-# greedy and generic-rollout forwards, whose callers never look at the error word, keep the one-workgroup launch.
+# answers by dropping to the one-workgroup launch and redoing the rollout (Runner.generate_rollout).  Only a forward called
+# with `encode(..., chain_split=True)` (the Runner's pipelined rollout passes it, and checks) takes the split launch:
+# evaluation, greedy and generic-rollout forwards, whose callers never look at the error word, keep the one-workgroup launch.
 CHAIN_SPLIT = int(os.environ.get("PPO_AMD_CHAIN_SPLIT", "1"))
 CHAIN_SPLIT_MAX_BATCH = 128
 # ... and its backward-data pass (blocks + max-pool backward + transposed first convolution) likewise.  Off by default:
@@ -455,19 +455,12 @@ class DualHeadNet:
         self._build_tvf_feature_mask()
         self._bufs: Dict[tuple, torch.Tensor] = {}
         self._rec = None   # launch recorder (see encode)
-        # (n_actions, temperature, seed, offset, log_policy, actions, log_pac, raw_policy, values, n_value_heads) of
-        # ppo_dense_heads_act_forward_f32, set by the caller of an inference encode(); None again once a launch took it
-        # (_dense_heads, or encode()'s replay of a recorded launch list)
-        self.act_tail = None
         self._chain_split_usable = None  # decided at the first split launch (see _chain_split_first_use)
-        self.allow_chain_split = False   # set by a caller that checks chain_split_error() afterwards
-        self.obs_index = None  # [B] int32 (device): the next TRAINING forward reads observation i at x[obs_index[i]] (see takes_obs_index)
-        self.loss_tail = None  # arguments of the PPO loss for the next training forward's dense + heads launch (ppo_minibatch)
         self._tail_ptrs = {}  # pointer arrays of the fused stack kernels, by stack index or (form, stack index): _packed_ptrs
         self.obs_norm = None  # shared ObsNormalizer (set by TVFModel when observation_normalization is on)
         self.grad_ready_hook = None  # callable(stream), see _backward_impala (data-parallel gradient buckets)
         self._split_ws = {}  # workspaces of the two-workgroups-per-image chain launch
-        self._plans = {}   # (tag, batch, dtype) -> recorded inference launch list
+        self._plans = {}   # (tag, batch, dtype, chain_split) -> recorded inference launch list
         self.use_plans = True  # False: every inference launch goes through _call (bench.py's per-kernel table brackets it)
         self._find_generic_convs()
         self._build_packed_weights()
@@ -844,11 +837,22 @@ class DualHeadNet:
         self._call("ppo_conv3x3_forward_f32", _p(x), mode, _p(self.params[wname + ".weight"]),
                    _p(self.params[wname + ".bias"]), _p(residual), _p(out), n, cin, cout, h, w)
 
-    def encode(self, x: torch.Tensor, train: bool, tag: Optional[str] = None):
+    def encode(self, x: torch.Tensor, train: bool, tag: Optional[str] = None, *, index=None, tail=None, chain_split=False):
         """x: [B, *input_dims] uint8 (scaled /255 on load; impala only) or float32.  Returns the dict of
         saved tensors; 'h' is the encoder output before the encoder activation, 'hact' its tanh when the
         activation is tanh.  `tag` names the scratch-buffer set ("t" training, "i" inference by default);
-        forwards that overlap on different streams use different tags."""
+        forwards that overlap on different streams use different tags.
+        `index`: [B] int32 (device), a training forward only: sample b is x[index[b]] and B = len(index), on a net
+        that can read its observations through it (takes_obs_index); anything else raises ValueError.
+        `tail`: the arguments that ride on the dense + heads launch (_dense_heads) behind the ones every form of it
+        takes.  Training: those of the discrete PPO loss on the finished head row, ppo_dense_heads_loss_forward_f32's
+        (n_actions, n_value_heads, actions, old_log_pac, old_log_policy, advantages, returns, eps_clip, ent_coef, vf_coef,
+        grad_scale, dheads, stats, index).  Inference: those of the rollout's action step, ppo_dense_heads_act_forward_f32's
+        (n_actions, temperature, seed, offset, log_policy, actions, log_pac, raw_policy, values, n_value_heads).  The
+        result's 'tail_taken' says whether a launch took them (always a bool; False without a tail, and on a net that has
+        no such launch): if not, the caller launches the loss or the action step itself.
+        `chain_split`: an inference forward may take the two-workgroups-per-image chained launch (CHAIN_SPLIT); the
+        caller checks chain_split_error() afterwards."""
         sp = self.spec
         tag = tag or ("t" if train else "i")
         self._refresh_packed()
@@ -856,25 +860,29 @@ class DualHeadNet:
             raise ValueError(f"expected input [B, {sp.input_dims}], got {tuple(x.shape)}")
         if x.dtype not in (torch.uint8, torch.float32) or not x.is_contiguous() or x.device != self.device:
             raise ValueError("input must be a contiguous uint8/float32 tensor on the model's device")
+        if index is not None and not (train and self.takes_obs_index(x)):
+            raise ValueError("index: a training forward only, on a net that reads observations through it (takes_obs_index)")
         # Inference forwards (the rollout: 2 x 257 per iteration, with the host on the critical path) replay a
         # recorded launch list: every pointer and size of a (tag, batch) forward is fixed — scratch buffers
         # persist, parameters are views of one flat buffer — except the input, which is patched in.  That cuts
         # the per-launch Python work to the ctypes call itself.
-        key = (tag, x.shape[0], x.dtype, self.allow_chain_split)
+        key = (tag, x.shape[0], x.dtype, chain_split)
         plan = None if train or not self.use_plans else self._plans.get(key)
         if plan is not None:
-            calls, acts, x_slots = plan
+            calls, acts, x_slots, heads_at = plan
+            taken = tail is not None and heads_at is not None
+            if taken:
+                # the rollout's action step rides on the dense + heads launch: the recorded plain form gives way to the
+                # action form with this env step's tail
+                calls = list(calls)
+                calls[heads_at] = (self.lib.ppo_dense_heads_act_forward_f32, "ppo_dense_heads_act_forward_f32",
+                                   (*calls[heads_at][2], *tail))
             st, xp = _lib.current_stream(), x.data_ptr()
             for k, (fn, fn_name, args) in enumerate(calls):
-                if self.act_tail is not None and fn_name == "ppo_dense_heads_forward_f32":
-                    # the rollout's action step rides on the dense + heads launch (Runner._policy_step set the tail)
-                    fn_name, tail, self.act_tail = "ppo_dense_heads_act_forward_f32", self.act_tail, None
-                    rc = self.lib.ppo_dense_heads_act_forward_f32(*args, *tail, st)
-                else:
-                    rc = fn(xp, *args[1:], st) if k in x_slots else fn(*args, st)
+                rc = fn(xp, *args[1:], st) if k in x_slots else fn(*args, st)
                 if rc != 0:
                     _lib.check(rc, fn_name)
-            out = dict(acts)
+            out = dict(acts, tail_taken=taken)
             if self.obs_norm is None:
                 for name in plan_input_keys(self.encoder_kind):
                     out[name] = x
@@ -890,8 +898,9 @@ class DualHeadNet:
                 self._call("ppo_obs_normalize_f32", _p(x), 1 if x.dtype == torch.uint8 else 0, _p(self.obs_norm.mu),
                            _p(self.obs_norm.std), self.obs_norm.norm_eps, _p(x_in), x.shape[0], self.obs_norm.F)
             acts = (self._encode_mlp(x_in, train, tag) if self.encoder_kind == "mlp"
-                    else self._encode_nature(x_in, train, tag) if self.encoder_kind == "nature"
-                    else self._encode_impala(x_in, train, tag))
+                    else self._encode_nature(x_in, train, tag, tail) if self.encoder_kind == "nature"
+                    else self._encode_impala(x_in, train, tag, index, tail, chain_split))
+            acts.setdefault("tail_taken", False)  # (no dense + heads launch on this path)
             if self.encoder_activation_fn == "tanh" and "heads" not in acts:
                 h = acts["h"]
                 hact = self._buf(tag + "hact", tuple(h.shape))
@@ -900,7 +909,9 @@ class DualHeadNet:
             if self._rec is not None:
                 xp = x.data_ptr()
                 x_slots = frozenset(k for k, (_f, _n, a) in enumerate(self._rec) if a and a[0] == xp)
-                self._plans[key] = (self._rec, {k: v for k, v in acts.items() if v is not x}, x_slots)
+                # where a replay with a tail puts the action form (the plain form is what _dense_heads records)
+                heads_at = next((k for k, (_f, n, _a) in enumerate(self._rec) if n == "ppo_dense_heads_forward_f32"), None)
+                self._plans[key] = (self._rec, {k: v for k, v in acts.items() if v is not x}, x_slots, heads_at)
         finally:
             self._rec = None
         return acts
@@ -924,7 +935,7 @@ class DualHeadNet:
         self._linear(a1, sp.hidden_units, "encoder.fc2", h, tag=tag)
         return {"x": x, "a1": a1, "h": h}
 
-    def _encode_nature(self, x, train, tag):
+    def _encode_nature(self, x, train, tag, tail):
         """NatureCNN.forward (rl/models.py:130-145), one launch per layer: three strided convolutions with the ReLU in
         their stores, then the linear layer - with the heads (and the action step or the PPO loss) in the same call when
         the encoder activation is relu, as behind the IMPALA encoder."""
@@ -938,39 +949,37 @@ class DualHeadNet:
             acts[name] = y
             cur, mode = y, IN_NONE
         # conv3's output is already through its ReLU
-        return self._dense_heads(cur.view(B, sp.flat), 0, "encoder.fc", tag, train, acts)
+        return self._dense_heads(cur.view(B, sp.flat), 0, "encoder.fc", tag, train, acts, tail)
 
-    def _dense_heads(self, flat, relu_x, wname, tag, train, acts):
+    def _dense_heads(self, flat, relu_x, wname, tag, train, acts, tail):
         """The encoder's last linear layer `wname` on relu(flat) (relu_x = 1) or flat (0), and - where the encoder
         activation is relu - the fused heads behind it in the same launch (the K-slice reduction of the dense product and
-        the heads share it; heads() hands the result out).  That launch also takes the discrete PPO loss on the finished
-        head row (a training forward under `loss_tail`: no loss launch) or the rollout's action step (an inference
-        forward under `act_tail`); either attribute is None again once a launch took it.  Fills acts' 'flat', 'h' and,
-        with the fused launch, 'heads'."""
+        the heads share it; heads() hands the result out).  That launch also takes `tail` (see encode): the discrete PPO
+        loss on the finished head row (a training forward: no loss launch) or the rollout's action step (an inference
+        forward).  Fills acts' 'flat', 'h', 'tail_taken' and, with the fused launch, 'heads'."""
         sp, B = self.spec, flat.shape[0]
         h = self._buf(f"{tag}h", (B, sp.hidden_units))
-        if self.encoder_activation_fn == "relu":
+        fused = self.encoder_activation_fn == "relu"
+        if fused:
             o = self._buf(f"{tag}heads", (B, self.nh))
             ws_bytes = self.lib.ppo_gemm_workspace_bytes(B, sp.hidden_units, sp.flat)
             ws = self._ws("gemm_ws" + tag, ws_bytes)
             args = (_p(flat), relu_x, _p(self.params[wname + ".weight"]), _p(self.params[wname + ".bias"]), _p(self.w_heads),
                     _p(self.b_heads), 1, _p(h), _p(o), B, sp.flat, sp.hidden_units, self.nh, _p(ws), ws_bytes)
-            if train and self.loss_tail is not None:
-                tail, self.loss_tail = self.loss_tail, None
+            if tail is None:
+                self._call("ppo_dense_heads_forward_f32", *args)
+            elif train:
                 self._call("ppo_dense_heads_loss_forward_f32", *args, *tail)
-            elif self.act_tail is not None and not train:
+            else:
                 # the recorded launch list keeps the plain form: its replay adds the tail of its own env step (see encode)
-                tail, self.act_tail = self.act_tail, None
                 with self._unrecorded() as rec:
                     self._call("ppo_dense_heads_act_forward_f32", *args, *tail)
                 if rec is not None:
                     rec.append((self.lib.ppo_dense_heads_forward_f32, "ppo_dense_heads_forward_f32", args))
-            else:
-                self._call("ppo_dense_heads_forward_f32", *args)
             acts["heads"] = o
         else:
             self._linear(flat, sp.flat, wname, h, relu_x=relu_x, tag=tag)
-        acts["flat"], acts["h"] = flat, h
+        acts["flat"], acts["h"], acts["tail_taken"] = flat, h, fused and tail is not None
         return acts
 
     def _packed_ptrs(self, key, names, transposed, biases=False, split=None):
@@ -1029,7 +1038,7 @@ class DualHeadNet:
         return bool(words.any().item())
 
     def chain_split_armed(self) -> bool:
-        """Whether a forward under allow_chain_split may take the split launch (so its caller has to check for errors)."""
+        """Whether a forward with chain_split=True may take the split launch (so its caller has to check for errors)."""
         return bool(CHAIN_SPLIT) and self.encoder_kind == "impala" and self._chain_split_usable is not False
 
     def chain_split_disable(self):
@@ -1047,9 +1056,8 @@ class DualHeadNet:
         for ws in self._split_ws.values():
             ws[-16:].view(torch.int32)[3] = 1
 
-    def _encode_impala(self, x, train, tag):
+    def _encode_impala(self, x, train, tag, index, tail, chain_split):
         sp = self.spec
-        index = self.obs_index if train else None
         B = x.shape[0] if index is None else int(index.shape[0])
         acts = {"x": x, "in0_index": index}
         cur, cur_mode = x, (IN_U8 if x.dtype == torch.uint8 else IN_NONE)
@@ -1073,7 +1081,7 @@ class DualHeadNet:
                     launch = ("ppo_impala_stack_chain_forward_f32", _p(p_prev), ptrs_prev[0], ptrs_prev[1],
                               _p(pa0) if train else None, _p(pq0) if train else None, _p(pa1) if train else None,
                               _p(pq1) if train else None, full[0], full[1], *outs)
-                    if not train and CHAIN_SPLIT and self.allow_chain_split and self._chain_split_usable is not False \
+                    if not train and CHAIN_SPLIT and chain_split and self._chain_split_usable is not False \
                             and B <= CHAIN_SPLIT_MAX_BATCH and (cout, h, w) == (32, 21, 21):
                         # a rollout group (at most half as many images as CUs): every image on two workgroups that split
                         # the output channels of the 21x21 convolutions and exchange halves (bit-identical, ~0.7 x the time)
@@ -1121,8 +1129,8 @@ class DualHeadNet:
                 self._conv(cur, cur_mode, wname, c, None, B, cin, cout, h, w)
                 self._call("ppo_maxpool3x3s2_forward_f32", _p(c), _p(p), _p(idx), B, cout, h, w)
             split = self.split_bf16 and (si, 0) in self._pk16
-            tail = None if split else self._stack_tail_ptrs(si, cout, ho, wo, B)
-            if split or tail is not None:
+            tail_ptrs = None if split else self._stack_tail_ptrs(si, cout, ho, wo, B)
+            if split or tail_ptrs is not None:
                 a0, q0, a1, q1 = self._block_maps(tag, si, B)
                 _save_block_maps(acts, si, p, a0, q0, a1)
                 cur, cur_mode = q1, IN_NONE
@@ -1139,16 +1147,16 @@ class DualHeadNet:
                                _p(a0) if train else None, _p(q0) if train else None, _p(a1) if train else None, _p(q1), B, cout,
                                ho, wo)
                 continue
-            if tail is not None:
+            if tail_ptrs is not None:
                 nxt = sp.stacks[si + 1] if si + 1 < len(sp.stacks) else None
                 if FUSE_STACK_CHAIN and nxt is not None and (nxt[0], nxt[2], nxt[3]) == (cout, ho, wo) \
                         and self._stack_full_ptrs(si + 1, nxt[0], nxt[1], nxt[2], nxt[3]) is not None:
                     # the next stack's launch takes these blocks along (their output stays in LDS on the way)
-                    pending = (p, tail, (a0, q0, a1, q1))
+                    pending = (p, tail_ptrs, (a0, q0, a1, q1))
                     continue
                 # inference needs only the stack's output; training keeps the maps the backward pass reads
                 # (the 16-channel form re-reads q0 for its second block's skip connection: it is written in inference too)
-                self._call("ppo_impala_stack_tail_forward_f32", _p(p), tail[0], tail[1], _p(a0) if train else None,
+                self._call("ppo_impala_stack_tail_forward_f32", _p(p), tail_ptrs[0], tail_ptrs[1], _p(a0) if train else None,
                            _p(q0) if (train or cout == 16) else None, _p(a1) if train else None, _p(q1), B, cout, ho, wo)
                 continue
             q = p
@@ -1169,7 +1177,7 @@ class DualHeadNet:
                 acts[f"q{si}_{bi}_in"], acts[f"a{si}_{bi}"] = q, a
                 q = qn
             cur, cur_mode = q, IN_NONE
-        return self._dense_heads(cur.view(B, sp.flat), 1, "encoder.dense", tag, train, acts)
+        return self._dense_heads(cur.view(B, sp.flat), 1, "encoder.dense", tag, train, acts, tail)
 
     def _block_maps(self, tag, si, B):
         """The buffers (a0, q0, a1, q1) of stack si's two residual blocks in scratch-buffer set `tag`: per block the map
@@ -1256,14 +1264,12 @@ class DualHeadNet:
         return result
 
     # ------------------------------------------------------------------ backward
-    def backward(self, acts, dheads: torch.Tensor, accumulate: bool = False):
-        """Back-propagate d loss / d heads through heads and encoder into self.grad."""
+    def backward(self, acts, dheads: torch.Tensor):
+        """Back-propagate d loss / d heads through heads and encoder into self.grad, which it overwrites (the Runner sums
+        the passes of a minibatch split into micro-batches)."""
         sp = self.spec
         B = dheads.shape[0]
         H = sp.hidden_units
-        if accumulate:
-            raise NotImplementedError("micro-batch gradient accumulation is not built: with 288 GB of HBM a whole "
-                                      "minibatch is one pass (rl/rollout.py:2331-2374 splits only to fit memory)")
         h = acts["h"]
         relu = self.encoder_activation_fn == "relu"
         hin = h if relu else acts["hact"]
@@ -1627,16 +1633,11 @@ class DualHeadNet:
                              "minibatch, or the array the index points into with obs_indexed=True")
         return B
 
-    def _train_forward(self, prev_state, index=None, obs_indexed=False):
+    def _train_forward(self, prev_state, index=None, obs_indexed=False, tail=None):
         self._minibatch_rows(prev_state, index, obs_indexed)
-        if obs_indexed:
-            if not self.takes_obs_index(prev_state):
-                raise ValueError("this net needs the gathered minibatch of observations (takes_obs_index is False)")
-            self.obs_index = index
-        try:
-            acts = self.encode(prev_state, train=True)
-        finally:
-            self.obs_index = None
+        if obs_indexed and not self.takes_obs_index(prev_state):
+            raise ValueError("this net needs the gathered minibatch of observations (takes_obs_index is False)")
+        acts = self.encode(prev_state, train=True, index=index if obs_indexed else None, tail=tail)
         o = self.heads(acts, "t")
         B = o.shape[0]
         return acts, o, B, self._buf("dheads", (B, self.nh))
@@ -1672,13 +1673,8 @@ class DualHeadNet:
                      _p(self._buf("dheads", (B, self.nh))), _p(stats), _p(index))
         # the loss rides on the dense + heads launch of the training forward where that launch exists (_dense_heads: image
         # encoders with relu; ppo_dense_heads_loss_forward_f32, bit-identical, one latency-bound launch less per minibatch)
-        self.loss_tail = loss_args
-        try:
-            acts, o, B, dheads = self._train_forward(prev_state, index, obs_indexed)
-            fused = self.loss_tail is None
-        finally:
-            self.loss_tail = None
-        if not fused:
+        acts, o, B, dheads = self._train_forward(prev_state, index, obs_indexed, tail=loss_args)
+        if not acts["tail_taken"]:
             self._call("ppo_ppo_loss_f32", _p(o), B, self.nh, *loss_args)
         self.backward(acts, dheads)
         return stats

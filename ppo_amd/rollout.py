@@ -398,13 +398,18 @@ class Runner:
         self.step = 0
 
     # ------------------------------------------------------------------ rollout
-    def _forward_heads(self, obs, tag):
+    def _forward_heads(self, obs, tag, tail=None, split_nets=()):
+        """The head rows of the policy and the value net for `obs`, and whether the policy net's forward took `tail`
+        (models.DualHeadNet.encode).  `split_nets`: see _rollout_pipelined."""
         pol, val = self.policy_net, self.value_net
-        hp = pol.heads(pol.encode(obs, train=False, tag=tag), tag)
-        hv = val.heads(val.encode(obs, train=False, tag=tag), tag) if self.dual else hp
-        return hp, hv
+        acts = pol.encode(obs, train=False, tag=tag, tail=tail, chain_split=any(n is pol for n in split_nets))
+        hp = pol.heads(acts, tag)
+        hv = hp
+        if self.dual:
+            hv = val.heads(val.encode(obs, train=False, tag=tag, chain_split=any(n is val for n in split_nets)), tag)
+        return hp, hv, acts["tail_taken"]
 
-    def _policy_step(self, t, lo=0, hi=None, tag="i"):
+    def _policy_step(self, t, lo=0, hi=None, tag="i", split_nets=()):
         """Forward + action sampling for envs [lo, hi) at env step t; writes those columns of row t of the
         rollout buffers.  The sampling counter is keyed by (rollout, t, env, action), so splitting the envs
         into groups does not change which action any env takes.  Dual architecture: the policy comes from
@@ -425,15 +430,13 @@ class Runner:
 
         values = None if self.dual else self.value.data_ptr() + first * self.value.stride(1) * 4
         discrete = self.action_dist == "discrete"
+        tail = None
         if discrete:
             # the sampling rides on the policy net's dense + heads launch (one launch less per group and env step; same
-            # bits) when that forward replays its recorded launch list (models.DualHeadNet.encode); otherwise the tail
-            # comes back and is launched below
-            pol.act_tail = (nA, 1.0, seed & (2**64 - 1), counter, row(self.log_policy), row(self.actions),
-                            row(self.log_pac), row(self.raw_policy), values, self.VH)
-        hp, hv = self._forward_heads(self.all_obs[t, lo:hi], tag)
-        sampled = discrete and pol.act_tail is None
-        pol.act_tail = None
+            # bits) where that net has one (models.DualHeadNet.encode); otherwise it is launched below
+            tail = (nA, 1.0, seed & (2**64 - 1), counter, row(self.log_policy), row(self.actions),
+                    row(self.log_pac), row(self.raw_policy), values, self.VH)
+        hp, hv, sampled = self._forward_heads(self.all_obs[t, lo:hi], tag, tail, split_nets)
 
         if sampled:
             pass
@@ -583,14 +586,6 @@ class Runner:
     def _rollout_pipelined(self, parts, split_nets=()):
         """`split_nets`: the networks whose forwards may take the two-workgroups-per-image launch during this rollout
         (the caller checks their error word afterwards)."""
-        self._split_nets_active = list(split_nets)
-        try:
-            self._rollout_pipelined_impl(parts)
-        finally:
-            for n in split_nets:
-                n.allow_chain_split = False
-
-    def _rollout_pipelined_impl(self, parts):
         N = self.N
         self.all_time[0] = self.time
         rew_np, done_np = self._rewards_host.numpy(), self._dones_host.numpy()
@@ -616,8 +611,6 @@ class Runner:
         for s_ in streams:
             if s_ is not main:
                 s_.wait_stream(main)
-        for n in self._split_nets_active:
-            n.allow_chain_split = True
         norm = self.model.obs_norm
 
         # a group may be stepped (and uploaded) in several pieces: a leaf's H2D runs while the next leaf is stepped
@@ -643,7 +636,7 @@ class Runner:
             lo, hi = bounds[i], bounds[i + 1]
             torch.cuda.set_stream(streams[i])
             streams[i].wait_event(copy_events[i])
-            self._policy_step(t, lo, hi, tag=tags[i])
+            self._policy_step(t, lo, hi, tag=tags[i], split_nets=split_nets)
             if t < N:
                 host_rows[i].copy_(self.actions[t, lo:hi], non_blocking=True)
                 events[i].record()
@@ -694,7 +687,7 @@ class Runner:
                     for i in range(P):
                         torch.cuda.set_stream(streams[i])
                         streams[i].wait_event(self._norm_event)
-                        self._policy_step(t, bounds[i], bounds[i + 1], tag=tags[i])
+                        self._policy_step(t, bounds[i], bounds[i + 1], tag=tags[i], split_nets=split_nets)
                         if t < N:
                             host_rows[i].copy_(self.actions[t, bounds[i]:bounds[i + 1]], non_blocking=True)
                             events[i].record()

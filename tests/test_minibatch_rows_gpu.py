@@ -253,8 +253,13 @@ def test_impala_whole_batch_minibatch_reads_images_through_the_permutation(dims,
     assert "ppo_conv3x3_backward_weight_slabs_pooled_indexed_f32" in calls
     assert gmax > 0
     assert torch.equal(s_g, s_i) and torch.equal(g_g, net.grad)
-    assert net.obs_index is None
     got = {k: v.detach().cpu().numpy().copy() for k, v in net.grads.items()}
+    # the index was an argument of that call and nothing of it stays on the net: a plain gathered minibatch afterwards
+    # gives the gathered bits again
+    net.grad.zero_()
+    s_n = net.ppo_minibatch(gathered, actions, pac, lp, adv, ret, index=idx).clone()
+    assert torch.equal(s_g, s_n) and torch.equal(g_g, net.grad)
+    assert not [a for a in ("obs_index", "loss_tail", "act_tail", "allow_chain_split") if hasattr(net, a)]
 
     def float64_grads(images, kinks):
         """d ppo_loss / d parameters in float64 on the CPU: row b = images[b] with the kinks of `kinks`, paired with the

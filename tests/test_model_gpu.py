@@ -441,14 +441,14 @@ def test_two_workgroups_per_image_chain_launch_is_bit_identical(gold, monkeypatc
     for split in (0, 1):
         monkeypatch.setattr(models, "CHAIN_SPLIT", split)
         net = make_net(meta)
-        net.allow_chain_split = True  # (the Runner's pipelined rollout sets this; other forwards keep one workgroup per image)
         calls = []
         orig = net._call
         net._call = lambda fn, *a: (calls.append(fn), orig(fn, *a))[1]
         res = []
         for inp in (x, x2, x):
-            o = net.forward(inp)
-            res.append((o["raw_policy"].clone(), o["value"].clone()))
+            # chain_split: the Runner's pipelined rollout passes this; other forwards keep one workgroup per image
+            o = net.heads(net.encode(inp, False, chain_split=True), "i")  # the whole head row: raw_policy, value and the rest
+            res.append((o[:, :net.n_actions].clone(), o[:, net.n_actions:].clone()))
         torch.cuda.synchronize()
         assert ("ppo_impala_stack_chain_split_forward_f32" in calls) == bool(split)
         assert not net.chain_split_error()

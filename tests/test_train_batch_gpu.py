@@ -163,4 +163,9 @@ def test_minibatch_read_through_the_permutation_equals_the_gathered_minibatch():
     torch.cuda.synchronize()
     assert "ppo_conv3x3_pool_forward_packed_indexed_f32" in calls and "ppo_conv3x3_backward_weight_slabs_pooled_indexed_f32" in calls
     assert torch.equal(s_g, s_i) and torch.equal(g_g, net.grad) and float(g_g.abs().max()) > 0
-    assert net.obs_index is None
+    # the index was an argument of that call and nothing of it stays on the net: a plain gathered minibatch afterwards
+    # gives the gathered bits again
+    net.grad.zero_()
+    s_n = net.ppo_minibatch(gathered, actions, pac, lp, adv, ret, index=idx).clone()
+    assert torch.equal(s_g, s_n) and torch.equal(g_g, net.grad)
+    assert not [a for a in ("obs_index", "loss_tail", "act_tail", "allow_chain_split") if hasattr(net, a)]

@@ -146,7 +146,7 @@ def _four_convolutions(c, geom):
 
 def _chain_split(c, geom):
     # the two-workgroup form exists for the 32-channel 21x21 -> 11x11 chain only (the 84x84 net); the 64x64 net
-    # keeps the one-workgroup chain under allow_chain_split
+    # keeps the one-workgroup chain with chain_split=True
     want = "ppo_impala_stack_chain_split_forward_f32" if geom == "84x84" else "ppo_impala_stack_chain_forward_f32"
     return want in names_of(c)
 
@@ -197,7 +197,7 @@ def _separate_pool(c, geom):
     return n.count("ppo_maxpool3x3s2_forward_f32") == 2 and not any("conv3x3_pool_forward" in f for f in n)
 
 
-# name -> (module switches, allow_chain_split, first-layer form or None, "the kernel this plan is about ran")
+# name -> (module switches, encode's chain_split, first-layer form or None, "the kernel this plan is about ran")
 INFERENCE_PLANS = {
     "four-convolutions": (dict(FUSE_STACK_TAIL=0, FUSE_BLOCK=0), False, None, _four_convolutions),
     "defaults": ({}, False, None, _defaults),
@@ -227,10 +227,10 @@ def run_inference_plan(geom, x, plan):
         with switches(**sw):
             net = impala_net(geom)
             net.load_state_dict(impala_parameters(geom))
-            net.allow_chain_split = allow_split
             calls = record_calls(net)
-            row = net.forward(x)["_heads"].clone()
-            replayed = net.forward(x)["_heads"].clone()  # the recorded launch list, with its cached pointers
+            row = net.heads(net.encode(x, False, chain_split=allow_split), "i").clone()
+            # the recorded launch list, with its cached pointers
+            replayed = net.heads(net.encode(x, False, chain_split=allow_split), "i").clone()
             torch.cuda.synchronize()
     finally:
         lib.ppo_conv1_pool_form(before)

@@ -16,6 +16,7 @@ fresh net per case.
 import argparse
 import contextlib
 import ctypes
+import inspect
 import json
 import os
 import sys
@@ -119,7 +120,10 @@ def record(root, out_path):
     def infer(t, net, dims, allow_chain_split=False, uint8=True):
         x = observations(seeded(1), B, dims, uint8)
         t.hook(net)
-        net.allow_chain_split = allow_chain_split
+        if "chain_split" in inspect.signature(net.encode).parameters:
+            net.heads(net.encode(x, train=False, chain_split=allow_chain_split), "i")
+            return
+        net.allow_chain_split = allow_chain_split  # a checkout from before encode() took it as an argument
         try:
             net.heads(net.encode(x, train=False), "i")
         finally:
