@@ -481,6 +481,40 @@ int ppo_distil_loss_f32(const float *heads, int B, int ldo, int n_actions, int p
                         const int32_t *index, void *stream);
 
 /*
+ * The distillation-phase loss with the reference's other choices (rl/config.py:329-347); ppo_distil_loss_f32 is this
+ * entry with zero in every added argument, bit for bit.  Write d = P - T and w for the head weight:
+ *   value_loss (--distil_value_loss, rl/rollout.py:1370-1383), per prediction, then * w * vscale as above:
+ *     PPO_DISTIL_VALUE_MSE          0.5 d^2                                   d/dP = d
+ *     PPO_DISTIL_VALUE_L1           l1_scale |d|                              l1_scale sign(d), sign(0) = 0
+ *     PPO_DISTIL_VALUE_CLIPPED_MSE  clip(d, -1, 1)^2 (no 1/2)                 2 d on -1 <= d <= 1 (torch.clip), else 0
+ *     PPO_DISTIL_VALUE_HUBER        delta > 0: 0.5 d^2 if |d| < delta, else delta (|d| - 0.5 delta)
+ *                                                                             d, resp. delta sign(d)
+ *                                   delta == 0: |d|                           sign(d)
+ *   policy_loss (--distil_loss, :1407-1412), discrete policies only (log_std != NULL ignores it, :1397-1405), then * beta;
+ *   lp = log_softmax(z), p = exp(lp):
+ *     PPO_DISTIL_POLICY_KL          sum_a p_a (lp_a - old_a)                  old_policy = old log-probabilities
+ *     PPO_DISTIL_POLICY_MSE_POLICY  0.5 mean_a (old_a - lp_a)^2               d/dz_j = [(lp_j - old_j) - p_j sum_a (lp_a - old_a)] / n_actions
+ *     PPO_DISTIL_POLICY_MSE_LOGIT   0.5 mean_a (old_a - z_a)^2                old_policy = old raw logits; d/dz_j = (z_j - old_j) / n_actions
+ *   pred_actions (nullable, [*] int32 read through index like targets; --distil_target return | advantage, :1364-1368):
+ *     the one prediction of sample b is heads[b, pred_col + pred_actions[b]], the advantage head's entry for the action
+ *     taken; the other columns get gradient 0.  Needs n_pred == 1, scalar targets and pred_col + n_actions <= ldo.  An
+ *     action outside [0, n_actions) cannot be refused before the launch: that sample gets no value gradient and NaN in
+ *     its value, total and squared-error statistics.
+ *   n_active (--distil_max_heads, :1336-1362, 1386-1390; 0 = n_pred): the number of heads whose weight is not 0; the
+ *     loss is sqrt(n_active) mean over those heads, i.e. vscale = 1 / sqrt(n_active), and the squared-error statistic
+ *     divides by n_active.  `weights` carries w_k on the chosen heads and 0 elsewhere.
+ * PPO_E_INVALID before any launch: unknown mode, delta < 0, pred_actions with n_pred != 1 or vector_targets,
+ * n_active > n_pred.
+ */
+enum { PPO_DISTIL_POLICY_KL = 0, PPO_DISTIL_POLICY_MSE_POLICY = 1, PPO_DISTIL_POLICY_MSE_LOGIT = 2 };
+enum { PPO_DISTIL_VALUE_MSE = 0, PPO_DISTIL_VALUE_L1 = 1, PPO_DISTIL_VALUE_CLIPPED_MSE = 2, PPO_DISTIL_VALUE_HUBER = 3 };
+int ppo_distil_loss_modes_f32(const float *heads, int B, int ldo, int n_actions, int pred_col, int n_pred, int pred_stride,
+                              int vector_targets, const float *targets, const float *weights, const float *old_policy,
+                              const float *log_std, float beta, float grad_scale, float *dheads, float *stats,
+                              const int32_t *index, int policy_loss, int value_loss, float delta, float l1_scale,
+                              const int32_t *pred_actions, int n_active, void *stream);
+
+/*
  * Gaussian policy (action_dist "gaussian", rl/rollout.py:643-648): mu = heads[b, :n_actions],
  * action = mu + exp(log_std) * n with n ~ N(0,1) from `normal` [B,n_actions] if given, else Box-Muller on the
  * counter-based uniform stream keyed by (seed, offset + b*n_actions + a); deterministic != 0 -> action = mu.
@@ -895,6 +929,11 @@ typedef struct ppo_mlp_loss {
     const float *old_log_pac, *old_log_policy, *advantages;
     float eps_clip, ent_coef;
     float *dlog_std_rows; /* gaussian: [B, n_actions] scratch */
+    /* distil, the added arguments of ppo_distil_loss_modes_f32 (zero = ppo_distil_loss_f32) */
+    int distil_policy_loss, distil_value_loss; /* PPO_DISTIL_POLICY_*, PPO_DISTIL_VALUE_* */
+    float distil_delta, distil_l1_scale;
+    const int32_t *pred_actions;
+    int n_active;
 } ppo_mlp_loss;
 int ppo_mlp_supported(int F, int H, int NH);
 int ppo_mlp_forward_f32(const float *x, const ppo_mlp_net *net, const int32_t *index, int B, float *heads, float *h_pre,

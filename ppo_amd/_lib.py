@@ -103,6 +103,8 @@ SIGNATURES = {
     "ppo_tanh_backward_f32": (_i, [_vp, _vp, _vp, _sz, _vp]),
     "ppo_value_loss_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _f, _i, _i, _i, _vp, _vp, _f, _f, _vp, _vp, _vp, _f, _u64, _u64, _vp]),
     "ppo_distil_loss_f32": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp]),
+    "ppo_distil_loss_modes_f32": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _i, _i, _f, _f,
+                                       _vp, _i, _vp]),
     "ppo_gaussian_act_f32": (_i, [_vp, _i, _i, _i, _vp, _vp, _u64, _u64, _i, _vp, _vp, _vp, _vp, _i, _vp]),
     "ppo_gaussian_loss_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _vp, _vp, _vp, _vp, _vp]),
     "ppo_impala_stack_tail_supported": (_i, [_i, _i, _i]),
@@ -212,10 +214,16 @@ class MlpLoss(ctypes.Structure):
                 ("old_policy", ctypes.c_void_p), ("log_std", ctypes.c_void_p), ("beta", ctypes.c_float),
                 ("actions_f", ctypes.c_void_p), ("actions_i", ctypes.c_void_p), ("old_log_pac", ctypes.c_void_p),
                 ("old_log_policy", ctypes.c_void_p), ("advantages", ctypes.c_void_p), ("eps_clip", ctypes.c_float),
-                ("ent_coef", ctypes.c_float), ("dlog_std_rows", ctypes.c_void_p)]
+                ("ent_coef", ctypes.c_float), ("dlog_std_rows", ctypes.c_void_p),
+                ("distil_policy_loss", ctypes.c_int), ("distil_value_loss", ctypes.c_int),
+                ("distil_delta", ctypes.c_float), ("distil_l1_scale", ctypes.c_float),
+                ("pred_actions", ctypes.c_void_p), ("n_active", ctypes.c_int)]
 
 
 MLP_LOSS_VALUE, MLP_LOSS_DISTIL, MLP_LOSS_GAUSSIAN, MLP_LOSS_PPO = 1, 2, 3, 4
+# PPO_DISTIL_POLICY_* / PPO_DISTIL_VALUE_* (include/ppo_amd.h), by the reference's flag values
+DISTIL_POLICY_LOSSES = {"kl_policy": 0, "mse_policy": 1, "mse_logit": 2}
+DISTIL_VALUE_LOSSES = {"mse": 0, "l1": 1, "clipped_mse": 2, "huber": 3}
 
 
 class WgradJob(ctypes.Structure):

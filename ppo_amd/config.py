@@ -116,16 +116,23 @@ class EnvConfig(_Group):  # rl/config.py:495-603
 
 
 class DistilConfig(_Group):  # rl/config.py:329-354
+    LOSSES = ("mse_logit", "mse_policy", "kl_policy")
+    VALUE_LOSSES = ("mse", "clipped_mse", "l1", "huber")
+    TARGETS = ("return", "value", "advantage")
     FIELDS = (
         ("order", str, "after_policy", "[after_policy|before_policy]"),
         ("beta", float, 1.0, "weight of the policy constraint"),
-        ("target", str, "value", "[value]  (return / advantage targets are not built)"),
+        ("target", str, "value", "[return|value|advantage]  (return / advantage: GAE over the rollout against the "
+                                 "advantage head's entry for the action taken; discrete actions, no TVF, no replay)"),
         ("batch_size", int, -1, "distil batch size, negative = the rollout"),
+        ("adv_lambda", float, 0.6, "GAE lambda of the return / advantage distil targets"),
         ("period", int, 1, "distil every this many batches"),
-        ("loss", str, "kl_policy", "[kl_policy]"),
+        ("loss", str, "kl_policy", "[mse_logit|mse_policy|kl_policy]  (discrete policies; gaussian ones ignore it)"),
         ("max_heads", int, -1, "max TVF heads to distil, -1 = all"),
         ("force_ext", bool, False, "distil the ext value head even when TVF is on"),
-        ("value_loss", str, "mse", "[mse]"),
+        ("value_loss", str, "mse", "[mse|clipped_mse|l1|huber]"),
+        ("delta", float, 0.1, "delta of the huber value loss (0 = abs)"),
+        ("l1_scale", float, 1 / 30, "scale of the l1 value loss"),
         ("delay", float, 0, "millions of steps before distillation starts"),
         ("use_policy_opt", bool, False, "share the policy optimiser's moments"),
     )
@@ -478,6 +485,15 @@ class Config:
             raise ValueError("Invalid clip_mode.")
         if self.tvf.gamma is None:
             self.tvf.gamma = self.gamma
+        # the reference raises these two in the middle of an update (rl/rollout.py:1414, 2096; :1383 for the value loss)
+        if self.distil.loss not in DistilConfig.LOSSES:
+            raise ValueError(f"Invalid distil_loss {self.distil.loss}")
+        if self.distil.target not in DistilConfig.TARGETS:
+            raise ValueError(f"Invalid distil target {self.distil.target}")
+        if self.distil.value_loss not in DistilConfig.VALUE_LOSSES:
+            raise ValueError(f"Invalid loss distil loss {self.distil.value_loss}")
+        if self.distil.delta < 0:
+            raise ValueError(f"--distil_delta={self.distil.delta} must be >= 0")
         if self.rnd.enabled:
             assert self.observation_normalization, "RND requires observation normalization"  # rl/config.py:408-410
         if self.hash.bonus != 0:

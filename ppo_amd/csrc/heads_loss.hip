@@ -9,6 +9,10 @@
 //  * ppo_distil_loss_f32    distillation phase: 0.5 w_k (T_k - P_k)^2 [sqrt(K) mean_k when the targets are a
 //                           vector] + beta KL(pi_new || pi_old) (rl/rollout.py:1331-1449, value_loss "mse",
 //                           loss "kl_policy").
+//  * ppo_distil_loss_modes_f32   the same launch with the reference's other choices: value loss l1 | clipped_mse |
+//                           huber (:1370-1383), policy loss mse_policy | mse_logit (:1407-1412), the advantage head's
+//                           entry for the action taken as the prediction (:1364-1368), a subset of the TVF heads
+//                           (:1336-1362).
 //  * ppo_gaussian_act_f32   a = mu + exp(log_std) * n, n ~ N(0,1) by Box-Muller from the counter-based uniform
 //                           stream (rl/rollout.py:643-648), plus log N(a; mu, sigma) per dimension.
 //  * ppo_gaussian_loss_f32  clipped surrogate per action dimension, mean over dimensions, minus the value
@@ -163,8 +167,30 @@ extern "C" int ppo_distil_loss_f32(const float *heads, int B, int ldo, int n_act
         return fail(PPO_E_INVALID, "ppo_distil_loss_f32: bad shape");
     if (B == 0) return PPO_OK;
     if (!heads || !targets || !old_policy || !dheads) return fail(PPO_E_INVALID, "ppo_distil_loss_f32: null pointer");
+    return ppo_distil_loss_modes_f32(heads, B, ldo, n_actions, pred_col, n_pred, pred_stride, vector_targets, targets,
+                                     weights, old_policy, log_std, beta, grad_scale, dheads, stats, index,
+                                     PPO_DISTIL_POLICY_KL, PPO_DISTIL_VALUE_MSE, 0.f, 0.f, nullptr, 0, stream);
+}
+
+extern "C" int ppo_distil_loss_modes_f32(const float *heads, int B, int ldo, int n_actions, int pred_col, int n_pred,
+                                         int pred_stride, int vector_targets, const float *targets, const float *weights,
+                                         const float *old_policy, const float *log_std, float beta, float grad_scale,
+                                         float *dheads, float *stats, const int32_t *index, int policy_loss,
+                                         int value_loss, float delta, float l1_scale, const int32_t *pred_actions,
+                                         int n_active, void *stream)
+{
+    using namespace ppo;
+    if (B < 0 || n_actions <= 0 || n_actions > kMaxActions || n_pred <= 0 || pred_stride <= 0 || pred_col < n_actions ||
+        pred_col + (n_pred - 1) * pred_stride >= ldo)
+        return fail(PPO_E_INVALID, "ppo_distil_loss_modes_f32: bad shape");
+    const int rc = check_distil_modes("ppo_distil_loss_modes_f32", n_actions, pred_col, n_pred, vector_targets, ldo,
+                                      policy_loss, value_loss, delta, pred_actions, n_active);
+    if (rc) return rc;
+    if (B == 0) return PPO_OK;
+    if (!heads || !targets || !old_policy || !dheads)
+        return fail(PPO_E_INVALID, "ppo_distil_loss_modes_f32: null pointer");
     const DistilLossP p{ldo, n_actions, pred_col, n_pred, pred_stride, vector_targets, targets, weights, old_policy,
-                        log_std, beta, grad_scale, stats};
+                        log_std, beta, grad_scale, stats, policy_loss, value_loss, delta, l1_scale, pred_actions, n_active};
     hipLaunchKernelGGL(distil_loss_kernel, dim3((B + 3) / 4), dim3(256), 0, as_stream(stream), heads, B, p, dheads, index);
     return check_launch("distil_loss_kernel");
 }

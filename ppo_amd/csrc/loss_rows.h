@@ -79,19 +79,50 @@ __device__ __forceinline__ void value_loss_row(const ValueLossP &p, const float 
 
 // ---------------------------------------------------------------------------------------------- distillation phase
 enum { DS_VALUE = 0, DS_POLICY, DS_TOTAL, DS_SQERR, DS_N };
+// the modes of the reference's --distil_loss / --distil_value_loss (values of PPO_DISTIL_POLICY_* / PPO_DISTIL_VALUE_*)
+enum { DP_KL_POLICY = 0, DP_MSE_POLICY, DP_MSE_LOGIT, DP_N };
+enum { DV_MSE = 0, DV_L1, DV_CLIPPED_MSE, DV_HUBER, DV_N };
 struct DistilLossP {
     int ldo, nA, pred_col, n_pred, pred_stride, vector_targets;
     const float *targets, *weights, *old_policy, *log_std;
     float beta, grad_scale;
     float *stats;
+    // everything below: zero = kl_policy / mse / every head / the fixed prediction columns
+    int policy_loss, value_loss;  // DP_*, DV_*; uniform per launch
+    float delta, l1_scale;        // huber's delta (0 = plain abs), l1's scale
+    const int32_t *pred_actions;  // nullable: the one prediction of sample sb is column pred_col + pred_actions[sb]
+    int n_active;                 // heads with a non-zero weight (--distil_max_heads), 0 = n_pred
 };
+// the mode arguments of ppo_distil_loss_modes_f32 and of ppo_mlp_train_f32's distil loss, checked before any launch
+inline int check_distil_modes(const char *entry, int nA, int pred_col, int n_pred, int vector_targets, int ldo,
+                              int policy_loss, int value_loss, float delta, const int32_t *pred_actions, int n_active)
+{
+    if (policy_loss < 0 || policy_loss >= DP_N) return fail(PPO_E_INVALID, "%s: unknown policy_loss %d", entry, policy_loss);
+    if (value_loss < 0 || value_loss >= DV_N) return fail(PPO_E_INVALID, "%s: unknown value_loss %d", entry, value_loss);
+    if (!(delta >= 0.f)) return fail(PPO_E_INVALID, "%s: delta must be >= 0", entry);
+    if (pred_actions && (n_pred != 1 || vector_targets))
+        return fail(PPO_E_INVALID, "%s: pred_actions needs n_pred == 1 and a scalar target", entry);
+    if (pred_actions && pred_col + nA > ldo)
+        return fail(PPO_E_INVALID, "%s: pred_actions columns [%d, %d) exceed the row (%d)", entry, pred_col, pred_col + nA, ldo);
+    if (n_active < 0 || n_active > n_pred)
+        return fail(PPO_E_INVALID, "%s: n_active %d exceeds n_pred %d", entry, n_active, n_pred);
+    return PPO_OK;
+}
+
+__device__ __forceinline__ float sign0(float d) { return d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f); }
 __device__ __forceinline__ void distil_loss_row(const DistilLossP &p, const float *z, float *dz, int b, int sb, int lane)
 {
-    const int ldo = p.ldo, nA = p.nA, pred_col = p.pred_col, n_pred = p.n_pred, pred_stride = p.pred_stride,
-              vector_targets = p.vector_targets;
+    const int ldo = p.ldo, nA = p.nA, n_pred = p.n_pred, pred_stride = p.pred_stride, vector_targets = p.vector_targets;
     const float *targets = p.targets, *weights = p.weights, *old_policy = p.old_policy, *log_std = p.log_std;
     const float beta = p.beta, grad_scale = p.grad_scale;
     float *stats = p.stats;
+    const int policy_loss = p.policy_loss, value_loss = p.value_loss, n_active = p.n_active ? p.n_active : n_pred;
+    const float delta = p.delta, l1_scale = p.l1_scale;
+    // targets "return" / "advantage" (rl/rollout.py:1364-1368): the advantage head's entry for the action taken; an
+    // action outside [0, nA) matches no column, and the sample's statistics row says so with NaNs
+    const int act = p.pred_actions ? p.pred_actions[sb] : 0;
+    const bool bad_act = act < 0 || act >= nA;
+    const int pred_col = bad_act ? ldo : p.pred_col + act;
     // policy term over the nA policy outputs (nA <= 32 <= 64: one lane per action)
     const float logit = lane < nA ? z[lane] : -INFINITY;
     const float old = lane < nA ? old_policy[(size_t)sb * nA + lane] : 0.f;
@@ -104,17 +135,29 @@ __device__ __forceinline__ void distil_loss_row(const DistilLossP &p, const floa
         // the reference adds this term to the loss twice (rl/rollout.py:1409 and again :1419): keep its scale
         kl = 2.f * wave_sum(0.5f * d * d / den) / nA;
         gpol = 2.f * d / den / nA;
+    } else if (policy_loss == DP_MSE_LOGIT) {
+        // 0.5 mean_a (old_a - z_a)^2 on the raw logits (rl/rollout.py:1407-1408), old = the old raw policy
+        const float d = lane < nA ? logit - old : 0.f;
+        kl = 0.5f * wave_sum(d * d) / nA;
+        gpol = d / nA;
     } else {
-        // discrete: KL(new || old);  d KL / d z_j = p_j (log p_j - log q_j - KL)
         const float mx = wave_max(logit);
         const float e = lane < nA ? expf(logit - mx) : 0.f;
         const float lse = mx + logf(wave_sum(e));
         const float lp = logit - lse;
         const float p = lane < nA ? expf(lp) : 0.f;
-        kl = wave_sum(lane < nA ? p * (lp - old) : 0.f);
-        gpol = p * (lp - old - kl);
+        if (policy_loss == DP_MSE_POLICY) {
+            // 0.5 mean_a (old_a - lp_a)^2 (rl/rollout.py:1409-1410);  d / d z_j = [(lp_j - old_j) - p_j sum_a (lp_a - old_a)] / nA
+            const float d = lane < nA ? lp - old : 0.f;
+            kl = 0.5f * wave_sum(d * d) / nA;
+            gpol = (d - p * wave_sum(d)) / nA;
+        } else {
+            // discrete: KL(new || old);  d KL / d z_j = p_j (log p_j - log q_j - KL)
+            kl = wave_sum(lane < nA ? p * (lp - old) : 0.f);
+            gpol = p * (lp - old - kl);
+        }
     }
-    const float vscale = vector_targets ? 1.f / sqrtf((float)n_pred) : 1.f;
+    const float vscale = vector_targets ? 1.f / sqrtf((float)n_active) : 1.f;
     float vloss = 0.f, sq = 0.f;
     for (int c = lane; c < ldo; c += 64) {
         float g = 0.f;
@@ -124,21 +167,47 @@ __device__ __forceinline__ void distil_loss_row(const DistilLossP &p, const floa
             const int k = (c - pred_col) / pred_stride;
             const float w = weights ? weights[k] : 1.f;
             const float diff = z[c] - targets[(size_t)sb * n_pred + k];
-            vloss += 0.5f * vscale * w * diff * diff;
+            if (value_loss == DV_MSE) {
+                vloss += 0.5f * vscale * w * diff * diff;
+                g = vscale * w * diff;
+            } else {
+                // l: the loss of one prediction (rl/rollout.py:1370-1383), dl: d l / d P
+                const float ad = fabsf(diff);
+                float l, dl;
+                if (value_loss == DV_L1) {
+                    l = l1_scale * ad;
+                    dl = l1_scale * sign0(diff);
+                } else if (value_loss == DV_CLIPPED_MSE) {  // torch.clip passes the gradient on [-1, 1], bounds included
+                    const float cd = fminf(fmaxf(diff, -1.f), 1.f);
+                    l = cd * cd;
+                    dl = ad <= 1.f ? 2.f * diff : 0.f;
+                } else if (delta > 0.f && ad < delta) {  // huber, the quadratic zone
+                    l = 0.5f * diff * diff;
+                    dl = diff;
+                } else if (delta > 0.f) {
+                    l = delta * (ad - 0.5f * delta);
+                    dl = delta * sign0(diff);
+                } else {  // huber with delta 0 is abs (rl/rollout.py:1378-1379)
+                    l = ad;
+                    dl = sign0(diff);
+                }
+                vloss += vscale * w * l;
+                g = vscale * w * dl;
+            }
             sq += diff * diff * w * w;
-            g = vscale * w * diff;
         }
         dz[c] = grad_scale * g;
     }
     if (stats) {
         vloss = wave_sum(vloss);
         sq = wave_sum(sq);
+        if (bad_act) vloss = sq = NAN;
         if (lane == 0) {
             float *s = stats + (size_t)b * DS_N;
             s[DS_VALUE] = vloss;
             s[DS_POLICY] = beta * kl;
             s[DS_TOTAL] = vloss + beta * kl;
-            s[DS_SQERR] = sq / n_pred;
+            s[DS_SQERR] = sq / n_active;
         }
     }
 }

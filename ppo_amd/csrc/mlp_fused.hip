@@ -613,9 +613,15 @@ extern "C" int ppo_mlp_train_f32(const float *x, const ppo_mlp_net *net, const p
                 loss->pred_col < loss->n_actions || loss->pred_col + (loss->n_pred - 1) * loss->pred_stride >= NH ||
                 !loss->targets || !loss->old_policy)
                 return fail(PPO_E_INVALID, "ppo_mlp_train_f32: bad distil-loss arguments");
+            rc = check_distil_modes("ppo_mlp_train_f32", loss->n_actions, loss->pred_col, loss->n_pred, loss->vector_targets, NH,
+                                    loss->distil_policy_loss, loss->distil_value_loss, loss->distil_delta, loss->pred_actions,
+                                    loss->n_active);
+            if (rc) return rc;
             a.loss = MLP_LOSS_DISTIL;
             a.ld = DistilLossP{NH, loss->n_actions, loss->pred_col, loss->n_pred, loss->pred_stride, loss->vector_targets,
-                               loss->targets, loss->weights, loss->old_policy, loss->log_std, loss->beta, loss->grad_scale, loss->stats};
+                               loss->targets, loss->weights, loss->old_policy, loss->log_std, loss->beta, loss->grad_scale, loss->stats,
+                               loss->distil_policy_loss, loss->distil_value_loss, loss->distil_delta, loss->distil_l1_scale,
+                               loss->pred_actions, loss->n_active};
             break;
         case PPO_MLP_LOSS_GAUSSIAN:
             if (loss->n_actions <= 0 || loss->n_value_heads < 0 || NH < loss->n_actions + loss->n_value_heads || !loss->actions_f ||

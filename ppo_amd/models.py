@@ -1731,11 +1731,31 @@ class DualHeadNet:
         return stats
 
     def distil_minibatch(self, prev_state, targets, old_policy, beta=1.0, use_tvf=False, weights=None, gaussian=False,
-                         loss_scale=1.0, index=None, stat_sums=None, stat_accumulate=False, obs_indexed=False):
+                         loss_scale=1.0, index=None, stat_sums=None, stat_accumulate=False, obs_indexed=False,
+                         policy_loss="kl_policy", value_loss="mse", delta=0.0, l1_scale=0.0, pred_actions=None,
+                         head_subset=None):
         """Distillation phase (Runner.train_distil_minibatch, rl/rollout.py:1331-1449): targets [*] against the
         ext value head, or [*, K] against the TVF heads' ext column (use_tvf).  prev_state, ``index`` and
-        ``obs_indexed`` as in ppo_minibatch."""
+        ``obs_indexed`` as in ppo_minibatch.  policy_loss / value_loss (+ delta, l1_scale): --distil_loss /
+        --distil_value_loss by name; pred_actions [*] int32: the prediction is the advantage head's entry for that
+        action (targets "return" / "advantage", :1364-1368); head_subset: the TVF heads that take part
+        (--distil_max_heads), ``weights`` then being w_k on them and 0 elsewhere."""
         col, n_pred, stride = (self.col_tvf, self.K, self.vh) if use_tvf else (self.col_value, 1, 1)
+        if pred_actions is not None:
+            if use_tvf:
+                raise ValueError("pred_actions: a scalar target against the advantage head, not the TVF heads")
+            if pred_actions.dtype != torch.int32 or not pred_actions.is_contiguous():
+                raise ValueError("pred_actions must be contiguous int32")
+            col = self.col_advantage
+        n_active = 0
+        if head_subset is not None:
+            if not use_tvf or weights is None:
+                raise ValueError("head_subset: a subset of the TVF heads, with their weights")
+            n_active = len(head_subset)
+        try:
+            pl, vl = _lib.DISTIL_POLICY_LOSSES[policy_loss], _lib.DISTIL_VALUE_LOSSES[value_loss]
+        except KeyError as e:
+            raise ValueError(f"Invalid distil loss {e.args[0]}") from None
         if self.mlp_fused:
             B = self._minibatch_rows(prev_state, index, obs_indexed)
             return self._mlp_train(
@@ -1743,12 +1763,15 @@ class DualHeadNet:
                 obs_indexed=obs_indexed, grad_scale=float(loss_scale) / B, n_actions=self.n_actions, pred_col=col,
                 n_pred=n_pred, pred_stride=stride,
                 vector_targets=1 if use_tvf else 0, targets=_p(targets), weights=_p(weights), old_policy=_p(old_policy),
-                log_std=_p(self.params["log_std"]) if gaussian else None, beta=float(beta))
+                log_std=_p(self.params["log_std"]) if gaussian else None, beta=float(beta),
+                distil_policy_loss=pl, distil_value_loss=vl, distil_delta=float(delta), distil_l1_scale=float(l1_scale),
+                pred_actions=_p(pred_actions), n_active=n_active)
         acts, o, B, dheads = self._train_forward(prev_state, index, obs_indexed)
         stats = self._buf("distil_stats", (B, 4))
-        self._call("ppo_distil_loss_f32", _p(o), B, self.nh, self.n_actions, col, n_pred, stride, 1 if use_tvf else 0,
+        self._call("ppo_distil_loss_modes_f32", _p(o), B, self.nh, self.n_actions, col, n_pred, stride, 1 if use_tvf else 0,
                    _p(targets), _p(weights), _p(old_policy), _p(self.params["log_std"]) if gaussian else None,
-                   float(beta), float(loss_scale) / B, _p(dheads), _p(stats), _p(index))
+                   float(beta), float(loss_scale) / B, _p(dheads), _p(stats), _p(index), pl, vl, float(delta),
+                   float(l1_scale), _p(pred_actions), n_active)
         self.backward(acts, dheads)
         return stats
 

@@ -1156,6 +1156,39 @@ class Runner:
                 and self.batch_counter % args.distil.period == args.distil.period - 1
                 and (location is None or location == args.distil.order))
 
+    def _distil_old_policy_key(self):
+        """Which recorded policy the distil constraint compares against (rl/rollout.py:1397-1412): the raw policy - the
+        means of a gaussian policy, the logits under --distil_loss=mse_logit - or the log-policy."""
+        return "raw_policy" if self.action_dist == "gaussian" or args.distil.loss == "mse_logit" else "log_policy"
+
+    def _distil_head_weights(self, use_tvf):
+        """-> (weights, head_subset) of the distil loss: the duplicate-head weights of all TVF heads, or with
+        0 < --distil_max_heads < K those of even_sample_down's heads and 0 on the others (rl/rollout.py:1336-1362), a
+        device vector cached per subset.  Unlike tvf.subset_head_weights these carry no scale: the kernel takes the
+        sqrt(|S|) mean from its n_active."""
+        if not use_tvf:
+            return None, None
+        if not 0 < args.distil.max_heads < self.K:
+            return self._tvf_weights_dev, None
+        from .value_quality import even_sample_down
+        subset = [int(k) for k in even_sample_down(range(self.K), int(args.distil.max_heads))]
+        key = ("distil", tuple(subset))
+        dev = self._tvf_subset_weight_cache.get(key)
+        if dev is None:
+            w = np.zeros(self.K, np.float32)
+            w[subset] = self.tvf_weights[subset]
+            dev = self._tvf_subset_weight_cache[key] = torch.as_tensor(w, device=self.device)
+        return dev, subset
+
+    def _distil_step(self, prev_state, targets, old_policy, use_tvf, pred_actions=None, **kw):
+        """One distil minibatch under the --distil_* flags: what train_distil, train_distil_minibatch and the noise-scale
+        passes all run."""
+        weights, subset = self._distil_head_weights(use_tvf)
+        return self.policy_net.distil_minibatch(
+            prev_state, targets, old_policy, beta=args.distil.beta, use_tvf=use_tvf, weights=weights,
+            gaussian=self.action_dist == "gaussian", policy_loss=args.distil.loss, value_loss=args.distil.value_loss,
+            delta=args.distil.delta, l1_scale=args.distil.l1_scale, pred_actions=pred_actions, head_subset=subset, **kw)
+
     def get_distil_batch(self, samples_wanted=None):
         """Targets and the policy to stay close to, from the rollout (rl/rollout.py:2050-2112, the
         replay-free path): value_net's estimates recorded during the rollout, and either the rollout's
@@ -1168,17 +1201,35 @@ class Runner:
         if samples_wanted not in (None, B) or (0 < args.distil.batch_size != B):
             raise NotImplementedError("without a replay buffer (--replay_mode, --replay_size) distillation trains on the "
                                       "rollout: distil_batch_size = rollout")
-        if args.distil.target != "value" or args.distil.loss != "kl_policy" or args.distil.value_loss != "mse":
-            raise NotImplementedError("distil target 'value', loss 'kl_policy', value_loss 'mse' are built")
         use_tvf = self.tvf is not None and not args.distil.force_ext
-        if use_tvf and 0 < args.distil.max_heads < self.K:
-            raise NotImplementedError("distil_max_heads sub-sampling is not built (default: all heads)")
         batch = {"use_tvf": use_tvf}
         if use_tvf:
+            assert args.distil.target == "value", "Only value targets supported for TVF distil"
             batch["distil_targets"] = self.tvf.tvf_untrimmed_value[:N, :, :, 0].reshape(B, self.K)
-        else:
+        elif args.distil.target == "value":
             batch["distil_targets"] = self.ext_value[:N].reshape(B)  # (a view with one head, a copy of column 0 with two)
-        key = "raw_policy" if self.action_dist == "gaussian" else "log_policy"
+        else:
+            # "return" / "advantage" (:2077-2094): GAE(--distil_adv_lambda) of the rollout's rewards under value_net's
+            # recorded estimates, one scan; the "return" target is its ret output, f32(adv) + V.  Either is predicted by
+            # the advantage head's entry for the action taken (:1364-1368), so the batch carries the actions.
+            if self.action_dist != "discrete":
+                raise ValueError(f"--distil_target={args.distil.target} needs discrete actions: the advantage head is "
+                                 "indexed by the action taken")
+            net = self.policy_net
+            if self.VH > 1:  # the scan wants unit-stride rows
+                value = net._buf("distil_gae_value", (N + 1, A))
+                value.copy_(self.ext_value)
+            else:
+                value = self.value.view(N + 1, A)
+            targets = net._buf("distil_gae_targets", (N, A))
+            as_return = args.distil.target == "return"
+            self._call("ppo_gae_scan_f32", _p(self.ext_rewards), _p(value), _p(value[N]), _p(self.terminals),
+                       _lib.PPO_TERM_U8, None if as_return else _p(targets), _p(targets) if as_return else None, N, A, A,
+                       float(args.tvf.gamma), float(args.distil.adv_lambda), float(args.distil.adv_lambda),
+                       _lib.PPO_SCAN_AUTO)
+            batch["distil_targets"] = targets.view(B)
+            batch["distil_actions"] = self.actions.view(B)
+        key = self._distil_old_policy_key()
         if args.distil.order == "before_policy":
             old = getattr(self, key).view(B, self.n_actions)
         else:
@@ -1220,15 +1271,11 @@ class Runner:
         from value_net and the policy to stay close to from policy_net as they stand now, in chunks of
         --max_micro_batch_size.  Everything stays on the device."""
         assert args.distil.target == "value", "Replay distil required value targets."
-        if args.distil.loss != "kl_policy" or args.distil.value_loss != "mse":
-            raise NotImplementedError("distil loss 'kl_policy', value_loss 'mse' are built")
         use_tvf = self.tvf is not None and not args.distil.force_ext
-        if use_tvf and 0 < args.distil.max_heads < self.K:
-            raise NotImplementedError("distil_max_heads sub-sampling is not built (default: all heads)")
         obs, _aux = self.get_replay_sample(samples_wanted)
         S = int(obs.shape[0])
         pol, val = self.policy_net, self.value_net
-        key = "raw_policy" if self.action_dist == "gaussian" else "log_policy"
+        key = self._distil_old_policy_key()
         old = pol._buf("replay_distil_old_policy", (S, self.n_actions))
         targets = pol._buf("replay_distil_targets", (S, self.K) if use_tvf else (S,))
         chunk = max(args.max_micro_batch_size, 1)
@@ -1245,14 +1292,11 @@ class Runner:
             return
         batch = self.get_distil_batch()
         net = self.policy_net
-        gaussian = self.action_dist == "gaussian"
-        weights = self._tvf_weights_dev if batch["use_tvf"] else None
         net.zero_untouched_grads()
 
         def step(mb_obs, idx, loss_scale, **kw):
-            return net.distil_minibatch(mb_obs, batch["distil_targets"], batch["old_policy"], beta=args.distil.beta,
-                                        use_tvf=batch["use_tvf"], weights=weights, gaussian=gaussian,
-                                        loss_scale=loss_scale, index=idx, **kw)
+            return self._distil_step(mb_obs, batch["distil_targets"], batch["old_policy"], batch["use_tvf"],
+                                     pred_actions=batch.get("distil_actions"), loss_scale=loss_scale, index=idx, **kw)
         opt = self.policy_optimizer if args.distil.use_policy_opt else self.distil_optimizer
         # (with a replay buffer the batch is the sample drawn from it, otherwise the rollout where it lies)
         self._run_epochs("distil", Optimizer(net, args.distil_opt, opt.state), args.distil_opt.epochs,
@@ -1347,12 +1391,14 @@ class Runner:
         return {"loss": loss}
 
     def train_distil_minibatch(self, data, loss_scale=1.0, **kwargs):
+        """rl/rollout.py:1331-1449.  `data`: prev_state, distil_targets, old_log_policy or (gaussian policies,
+        --distil_loss=mse_logit) old_raw_policy, and with a --distil_target other than value distil_actions."""
         use_tvf = self.tvf is not None and not args.distil.force_ext
-        gaussian = self.action_dist == "gaussian"
-        stats = self.policy_net.distil_minibatch(
-            data["prev_state"], data["distil_targets"], data["old_raw_policy" if gaussian else "old_log_policy"],
-            beta=args.distil.beta, use_tvf=use_tvf, weights=self._tvf_weights_dev if use_tvf else None,
-            gaussian=gaussian, loss_scale=loss_scale)
+        actions = None
+        if not use_tvf and args.distil.target != "value":
+            actions = data["distil_actions"].to(torch.int32).contiguous()
+        stats = self._distil_step(data["prev_state"], data["distil_targets"], data["old_" + self._distil_old_policy_key()],
+                                  use_tvf, pred_actions=actions, loss_scale=loss_scale)
         total = stats[:, 2].double() * loss_scale
         return {"loss": float(total.mean()), "loss_std": float(total.std())}
 
