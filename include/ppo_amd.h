@@ -290,6 +290,38 @@ int ppo_conv3x3_any_backward_weight_f32(const void *in, int in_mode, const float
                                         int accumulate, void *stream);
 
 /* ------------------------------------------------------------------------
+ * 3x3 / stride 2 / zero-padding 1 convolution at ANY geometry (csrc/conv3x3_any.hip, csrc/conv3x3s2_any_index.h):
+ * torch.nn.Conv2d(cin, cout, 3, padding=1, stride=2) and its autograd - the stack-first convolution of the reference's
+ * IMPALA encoder under down_sample='stride' (rl/impala.py:96), which then has no max-pool.  n, cin, cout, h, w always
+ * describe the INPUT map; out / dy are [n, cout, (h+1)/2, (w+1)/2].  Three more operand descriptions on the tile loop
+ * of the family above: exact-f32 MFMA, padding taps zero by predicate, sums in a fixed order, every launch the same
+ * bits.  Untuned.
+ *
+ * ppo_conv3x3s2_any_supported: 1 for 1 <= cin, cout, h, w <= 4096, else 0.  What it rejects - and a batch n < 1, a null
+ *   required pointer or a tensor of 2^30 elements or more - every entry point rejects with PPO_E_INVALID before any
+ *   HIP call.
+ * ppo_conv3x3s2_any_forward_f32 (rl/impala.py:96):
+ *   out[img,co,oy,ox] = bias[co] + sum_{ci,ky,kx} f(in)[img,ci,2 oy+ky-1,2 ox+kx-1] * weight[co,ci,ky,kx] (+ residual);
+ *   in_mode PPO_IN_NONE | PPO_IN_RELU | PPO_IN_U8; bias, residual (of the output's shape) nullable.
+ * ppo_conv3x3s2_any_backward_data_f32 (autograd of rl/impala.py:96), gather form, no atomics: dx[img,ci,y,x] sums
+ *   dy[img,co,oy,ox] * weight[co,ci,ky,kx] over the (co,ky,kx) with y+1-ky = 2 oy, x+1-kx = 2 ox and (oy,ox) inside the
+ *   output; then * [relu_src > 0] (derivative 0 at 0) and + dres, both of the input's shape and nullable.
+ * ppo_conv3x3s2_any_backward_weight_f32 (autograd of rl/impala.py:96): the sum over (n, oy, ox) is cut into slabs
+ *   whose partial results (dbias among them) go to `workspace` - at least
+ *   ppo_conv3x3s2_any_wgrad_workspace_bytes(n, cin, cout, h, w) bytes - and are added up in ascending order by a second
+ *   launch; accumulate != 0 adds that sum into dweight / dbias.  dbias nullable.
+ * ---------------------------------------------------------------------- */
+int ppo_conv3x3s2_any_supported(int cin, int cout, int h, int w);
+int ppo_conv3x3s2_any_forward_f32(const void *in, int in_mode, const float *weight, const float *bias, const float *residual,
+                                  float *out, int n, int cin, int cout, int h, int w, void *stream);
+int ppo_conv3x3s2_any_backward_data_f32(const float *dy, const float *weight, const float *relu_src, const float *dres,
+                                        float *dx, int n, int cin, int cout, int h, int w, void *stream);
+size_t ppo_conv3x3s2_any_wgrad_workspace_bytes(int n, int cin, int cout, int h, int w);
+int ppo_conv3x3s2_any_backward_weight_f32(const void *in, int in_mode, const float *dy, float *dweight, float *dbias,
+                                          void *workspace, size_t workspace_bytes, int n, int cin, int cout, int h, int w,
+                                          int accumulate, void *stream);
+
+/* ------------------------------------------------------------------------
  * Strided convolutions without padding, any geometry (csrc/conv_strided.hip): the layers of the reference's
  * NatureCNN (rl/models.py:101-145: conv1 8x8 stride 4, conv2 4x4 stride 2, conv3 3x3 stride 1, F.relu behind each,
  * :135-137) and their autograd.  Implicit GEMMs on the exact-f32 MFMA, f32 accumulation in a fixed order: every

@@ -96,6 +96,11 @@ SIGNATURES = {
     "ppo_conv3x3_any_backward_data_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "ppo_conv3x3_any_wgrad_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "ppo_conv3x3_any_backward_weight_f32": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _vp]),
+    "ppo_conv3x3s2_any_supported": (_i, [_i, _i, _i, _i]),
+    "ppo_conv3x3s2_any_forward_f32": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "ppo_conv3x3s2_any_backward_data_f32": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "ppo_conv3x3s2_any_wgrad_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "ppo_conv3x3s2_any_backward_weight_f32": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _vp]),
     "ppo_conv3x3_backward_weight_bf16x3_supported": (_i, [_i, _i, _i, _i]),
     "ppo_conv3x3_backward_weight_slabs_batch_bf16x3": (_i, [_vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "ppo_conv3x3_wgrad_reduce_f32": (_i, [_vp, _i, _vp]),

@@ -186,15 +186,24 @@ class ImpalaSpec:
     """Static geometry of the IMPALA encoder (rl/models.py:54-99, rl/impala.py:85-123)."""
     kind = "impala"
 
-    def __init__(self, input_dims, channels=(16, 32, 32), n_block=2, hidden_units=256):
+    def __init__(self, input_dims, channels=(16, 32, 32), n_block=2, hidden_units=256, down_sample="pool",
+                 batch_norm=False):
+        if down_sample not in ("pool", "stride", "none"):
+            raise ValueError(f"Invalid down_sample mode {down_sample}")  # rl/impala.py:123
+        if batch_norm:
+            raise NotImplementedError("batch_norm=True: the IMPALA encoder's batch-norm layers have no HIP path")
         c, h, w = input_dims
         self.input_dims = tuple(input_dims)
         self.channels = tuple(channels)
         self.n_block = n_block
         self.hidden_units = hidden_units
+        # how a stack shrinks its map (rl/impala.py:96-123): 'pool' - first convolution at stride 1, then max-pool 3x3 /
+        # stride 2 / padding 1; 'stride' - first convolution at stride 2, no pool; 'none' - stride 1, no pool
+        self.down_sample = down_sample
         self.stacks = []  # (cin, cout, h_in, w_in, h_out, w_out)
         for cout in channels:
-            ho, wo = (h + 1) // 2, (w + 1) // 2
+            # floor((h + 2 - 3) / 2) + 1 == (h + 1) // 2 for the pool and for the strided convolution alike
+            ho, wo = (h, w) if down_sample == "none" else ((h + 1) // 2, (w + 1) // 2)
             self.stacks.append((c, cout, h, w, ho, wo))
             c, h, w = cout, ho, wo
         self.out_shape = (c, h, w)
@@ -401,7 +410,8 @@ class ObsNormalizer:
 class DualHeadNet:
     """One encoder + policy / value / advantage (/ TVF) heads (reference: rl/models.py:304-508), HIP-backed.
 
-    Encoders: ``impala`` (3x3 conv stacks, uint8 or float images), ``nature`` (three strided convolutions and a linear
+    Encoders: ``impala`` (3x3 conv stacks, uint8 or float images; encoder arguments ``channels``, ``n_block`` and
+    ``down_sample`` = 'pool' | 'stride' | 'none', see ImpalaSpec), ``nature`` (three strided convolutions and a linear
     layer, uint8 or float images; op-by-op launches in exact float32 whatever `precision`) and ``mlp`` (flat float
     observations);
     encoder activation ``relu`` (fused into the head GEMM's operand load) or ``tanh``.  All heads are ONE
@@ -546,7 +556,8 @@ class DualHeadNet:
         cjobs = []
         self._split_conv_jobs = None
         for si, (cin, cout, h, w, _ho, _wo) in enumerate(self.spec.stacks):
-            if not (self.split_bf16 and SPLIT_CONV and si > 0 and cin in (16, 32) and cout in (16, 32)):
+            if not (self.split_bf16 and SPLIT_CONV and si > 0 and cin in (16, 32) and cout in (16, 32)) \
+                    or self.spec.down_sample != "pool":  # (without the max-pool the first convolutions stay exact float32)
                 continue
             wname = f"encoder.stacks.{si}.firstconv"
             if wname in self._generic:
@@ -657,7 +668,9 @@ class DualHeadNet:
         the generic ppo_conv3x3_any_* ones, in exact float32 whatever `precision`.  Decided per convolution, by asking
         the specialised dispatchers' own probes: a net keeps every specialised and fused launch its other layers
         qualify for (a (12, 84, 84) net moves its first convolution only).  A generic convolution has no packed
-        weights, which is also what keeps the fused stack / block launches - all of them read packed weights - off it."""
+        weights, which is also what keeps the fused stack / block launches - all of them read packed weights - off it.
+        down_sample='stride' lists every stack's first convolution (its kernels are ppo_conv3x3s2_any_*);
+        down_sample='none' probes the blocks at the un-halved map, which is what `stacks` holds then."""
         self.generic_convs, self._probes = [], {}
         if self.encoder_kind == "impala":
             lib, sp = self.lib, self.spec
@@ -670,7 +683,13 @@ class DualHeadNet:
             for si, (cin, cout, h, w, ho, wo) in enumerate(sp.stacks):
                 # the observations arrive as uint8 or (normalised, or float environments) as float32; nothing
                 # back-propagates into them
-                if not specialised((IN_U8, IN_NONE) if si == 0 else (IN_NONE,), cin, cout, h, w, si > 0):
+                if sp.down_sample == "stride":
+                    # the stride-2 first convolution has the generic ppo_conv3x3s2_any_* kernels only: no packed weights,
+                    # no split-bf16 packing and no fused launch that contains it
+                    self.generic_convs.append(f"encoder.stacks.{si}.firstconv")
+                    if not lib.ppo_conv3x3s2_any_supported(cin, cout, h, w):
+                        raise _lib.PpoAmdError(f"no 3x3 stride-2 convolution kernel for {cin}->{cout} on {h}x{w}")
+                elif not specialised((IN_U8, IN_NONE) if si == 0 else (IN_NONE,), cin, cout, h, w, si > 0):
                     self.generic_convs.append(f"encoder.stacks.{si}.firstconv")
                     if not lib.ppo_conv3x3_any_supported(cin, cout, h, w):
                         raise _lib.PpoAmdError(f"no 3x3 convolution kernel for {cin}->{cout} on {h}x{w}")
@@ -1006,8 +1025,9 @@ class DualHeadNet:
         """Host arrays of the five packed-weight / bias pointers (firstconv + the four block convolutions) of stack
         si for the whole-stack kernel, or None when it does not apply."""
         if not (FUSE_STACK_FULL and FUSE_STACK_TAIL) or self.spec.n_block != 2 or cin != cout \
-                or not self.lib.ppo_impala_stack_full_supported(cout, h, w) or self.split_bf16:
-            return None  # (split mode: the blocks of the 32-channel stacks have their own launches)
+                or not self.lib.ppo_impala_stack_full_supported(cout, h, w) or self.split_bf16 \
+                or self.spec.down_sample != "pool":
+            return None  # (split mode: the blocks of the 32-channel stacks have their own launches; the kernel pools)
         return self._packed_ptrs(("full", si), _conv_names(si, firstconv=True), 0, biases=True)
 
     def _stack_tail_ptrs(self, si, cout, ho, wo, batch=1 << 30):
@@ -1062,9 +1082,10 @@ class DualHeadNet:
         acts = {"x": x, "in0_index": index}
         cur, cur_mode = x, (IN_U8 if x.dtype == torch.uint8 else IN_NONE)
         pending = None  # (pooled map, pointer arrays, output buffers) of a stack whose blocks the next launch runs
+        pool = sp.down_sample == "pool"
         for si, (cin, cout, h, w, ho, wo) in enumerate(sp.stacks):
             p = self._buf(f"{tag}p{si}", (B, cout, ho, wo))
-            idx = self._buf(f"{tag}idx{si}", (B, cout, ho, wo), torch.uint8) if train else None
+            idx = self._buf(f"{tag}idx{si}", (B, cout, ho, wo), torch.uint8) if train and pool else None
             wname = f"encoder.stacks.{si}.firstconv"
             acts[f"in{si}"], acts[f"idx{si}"] = cur, idx
             full = self._stack_full_ptrs(si, cin, cout, h, w) if cur_mode == IN_NONE else None
@@ -1101,7 +1122,15 @@ class DualHeadNet:
                 _save_block_maps(acts, si, p, a0, q0, a1)
                 cur, cur_mode = q1, IN_NONE
                 continue
-            if self.split_bf16 and (wname, 0) in self._pk16 and cur_mode != IN_U8 and cur.dtype == torch.float32:
+            if not pool:
+                # down_sample 'stride' | 'none' (rl/impala.py:96, 102-105): no max-pool, the first convolution - exact
+                # float32 at stride 2, or whatever _conv picks at stride 1 - writes the stack's map itself
+                if sp.down_sample == "stride":
+                    self._call("ppo_conv3x3s2_any_forward_f32", _p(cur), cur_mode, _p(self.params[wname + ".weight"]),
+                               _p(self.params[wname + ".bias"]), None, _p(p), B, cin, cout, h, w)
+                else:
+                    self._conv(cur, cur_mode, wname, p, None, B, cin, cout, h, w)
+            elif self.split_bf16 and (wname, 0) in self._pk16 and cur_mode != IN_U8 and cur.dtype == torch.float32:
                 # --precision=low|medium: the stack-first convolution as split-bf16 products, with the max-pool inside the
                 # launch or behind it
                 if self.lib.ppo_conv3x3_pool_bf16x3_supported(cin, cout, h, w):
@@ -1520,6 +1549,24 @@ class DualHeadNet:
             # max-pool backward, then the stack's first convolution
             x_in = acts[f"in{si}"]
             mode = IN_NONE if si > 0 else (IN_U8 if x_in.dtype == torch.uint8 else IN_NONE)
+            if sp.down_sample != "pool":
+                # no max-pool: g is the gradient of the first convolution's output
+                g_prev = self._buf(f"g{si - 1}_top", (B, cin, hh, ww)) if si > 0 else None
+                if sp.down_sample == "stride":
+                    nbytes = int(lib.ppo_conv3x3s2_any_wgrad_workspace_bytes(B, cin, cout, hh, ww))
+                    ws = self._ws("wgrad_ws_" + fc, nbytes)
+                    self._call("ppo_conv3x3s2_any_backward_weight_f32", _p(x_in), mode, _p(g), _p(self.grads[fc + ".weight"]),
+                               _p(self.grads[fc + ".bias"]), _p(ws), nbytes, B, cin, cout, hh, ww, 0)
+                    if si > 0:
+                        self._call("ppo_conv3x3s2_any_backward_data_f32", _p(g), _p(self.params[fc + ".weight"]), None, None,
+                                   _p(g_prev), B, cin, cout, hh, ww)
+                else:
+                    wgrad(x_in, mode, g, fc, B, cin, cout, hh, ww)
+                    if si > 0:
+                        self._call(self._bwd_data_fn(fc), _p(g), _p(self._bwd_w(fc)), None, None, _p(g_prev), B, cin, cout,
+                                   hh, ww)
+                g = g_prev
+                continue
             if si == 0 and WGRAD_POOLED_DY and fc not in self._generic \
                     and lib.ppo_conv3x3_backward_weight_pooled_supported(cin, cout, hh, ww):
                 # nothing else reads this stack's pre-pool gradient: the weight-gradient kernel forms it band by band
@@ -1560,7 +1607,7 @@ class DualHeadNet:
         fifth problem (WGRAD_RIDE): a c -> c convolution with a specialised kernel, on the geometry of that stack's four
         block convolutions.  (Its input is read raw: below the first stack no convolution reads uint8.)"""
         sp = self.spec
-        if not (WGRAD_RIDE and WGRAD_BATCH_LAUNCH) or si < 1 or sp.n_block != 2:
+        if not (WGRAD_RIDE and WGRAD_BATCH_LAUNCH) or si < 1 or sp.n_block != 2 or sp.down_sample != "pool":
             return False
         cin, cout, hh, ww, _ho, _wo = sp.stacks[si]
         return cin == cout and f"encoder.stacks.{si}.firstconv" not in self._generic \
@@ -1570,8 +1617,8 @@ class DualHeadNet:
         """Host array of the five backward-data packed weights of stack si in processing order (block1.conv1,
         block1.conv0, block0.conv1, block0.conv0, firstconv), or None when the whole-stack kernel does not apply."""
         if not (FUSE_STACK_FULL_BWD and FUSE_STACK_TAIL) or self.spec.n_block != 2 or cin != cout \
-                or not self.lib.ppo_impala_stack_full_supported(cout, h, w):
-            return None
+                or not self.lib.ppo_impala_stack_full_supported(cout, h, w) or self.spec.down_sample != "pool":
+            return None  # (the kernel reads the max-pool's argmax)
         return self._packed_ptrs(("full_bwd", si), _conv_names(si, reverse=True, firstconv=True), 1)
 
     def _stack_chain_bwd_ptrs(self, si, batch):
@@ -1580,6 +1627,7 @@ class DualHeadNet:
         per stack, both stacks of one channel count at a geometry the whole-stack kernels have, and a batch that fills
         the chip (one workgroup per image)."""
         if si < 1 or self.split_bf16 or batch < FUSE_CHAIN_BWD_MIN_BATCH or self.spec.n_block != 2 \
+                or self.spec.down_sample != "pool" \
                 or not (FUSE_STACK_TAIL and FUSE_STACK_TAIL_BWD >> si & 1 and FUSE_STACK_TAIL_BWD >> (si - 1) & 1):
             return None
         cin, cout, h, w, _ho, _wo = self.spec.stacks[si]
@@ -1613,7 +1661,7 @@ class DualHeadNet:
         IMPALA only, and only where the first convolution has its specialised kernels (the generic ones take the gathered
         minibatch): the nature and mlp op-by-op paths take the gathered minibatch."""
         if self.encoder_kind != "impala" or "encoder.stacks.0.firstconv" in self._generic or obs.dtype != torch.uint8 \
-                or self.obs_norm is not None or not GATHER_IN_CONV:
+                or self.obs_norm is not None or not GATHER_IN_CONV or self.spec.down_sample != "pool":
             return False
         cin, cout, h, w, _ho, _wo = self.spec.stacks[0]
         return bool(FUSE_POOL_STACKS & 1) and self._pk.get(("encoder.stacks.0.firstconv", 0)) is not None \
