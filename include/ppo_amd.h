@@ -924,6 +924,11 @@ int ppo_synth_env_set_state(void *env, const int64_t *steps, const int32_t *time
  *   `partials` / `n_partials`: per-workgroup sums of g^2 over everything written (for ppo_adam_step_presummed_f32).
  *   Gradients of parameters the loss does not reach are exact zeros (the reference leaves them None); dlog_std is
  *   written by every loss kind (zeros unless gaussian).
+ *   ppo_mlp_supported(F, H, NH): whether a training tile of the net fits the 160 KiB of LDS (and H % 16 == 0); both
+ *   entry points refuse, before any launch, a net it refuses.
+ *   The tensors of ppo_mlp_net may be free-standing allocations of exactly the stated sizes, each 4-byte aligned: no
+ *   byte outside them is read, whatever F, H and NH are, so what follows a tensor in memory (another parameter, padding,
+ *   NaN) never reaches a result (tests/test_mlp_fused_gpu.py puts NaN guards behind every one).
  */
 typedef struct ppo_mlp_net {
     const float *w1, *b1; /* fc1 [H, F], [H] */

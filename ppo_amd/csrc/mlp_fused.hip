@@ -65,6 +65,14 @@ struct MlpArgs {
 
 __host__ __device__ inline int lds_stride(int n) { int v = (n + 15) / 16 * 16; return v + ((4 - v % 32) + 32) % 32; }
 
+// A forward layer's weight matrix [N, K] as a buffer of exactly its own N * K floats: the 16-byte loads below are range
+// checked dword by dword, so whatever part of one lies behind the matrix reads as zero and no byte outside the tensor is
+// fetched (the matrices the LDS limit admits are far below the 2 GiB a 32-bit offset covers).
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t weights_of(const float *W, int N, int K)
+{
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(W), 0, N * K * 4, 0x00020000);
+}
+
 // Every phase of the rows kernel is a chain of dependent memory round trips (weights -> MFMAs -> bias -> LDS -> barrier),
 // and at one 16-row tile per CU nothing else hides them: measured per layer 6 - 10 us for 1.5 us of MFMA work, 15 us for
 // the loss (index -> target rows), 16 us for a store phase at the end (tools/mlp_phases.sh).  So: a layer's first blocks
@@ -87,7 +95,7 @@ __device__ __forceinline__ void fwd_issue(const float *__restrict__ W, const flo
 {
     const int l15 = lane & 15, g = lane >> 4;
     const int K16 = (K + 15) / 16;
-    const __amdgpu_buffer_rsrc_t wb = buffer_of(W), bb = buffer_of(bias, bias != nullptr);
+    const __amdgpu_buffer_rsrc_t wb = weights_of(W, N, K), bb = buffer_of(bias, bias != nullptr);
     const int n0 = wave * 16;
     const bool live = n0 < N;
     const int nrow = n0 + l15 < N ? n0 + l15 : N - 1;
@@ -125,10 +133,10 @@ __device__ __forceinline__ void fwd_layer(const float *__restrict__ W, const flo
 {
     const int l15 = lane & 15, g = lane >> 4;
     const int K16 = (K + 15) / 16;
-    // a 16-byte read that runs past the end of a row continues into the next row - or, for the last row, into whatever
-    // follows the matrix in the flat parameter buffer (at most 12 bytes: finite numbers): those k meet the zeros of the
-    // activation rows' padding
-    const __amdgpu_buffer_rsrc_t wb = buffer_of(W), bb = buffer_of(bias, bias != nullptr);
+    // a 16-byte read that runs past the end of a row continues into the next row, and those k meet the zeros of the
+    // activation rows' padding; behind the last row the matrix - and with it the buffer (weights_of) - ends, and the
+    // dwords past it come back as zeros without being fetched: W may be a free-standing tensor with anything behind it
+    const __amdgpu_buffer_rsrc_t wb = weights_of(W, N, K), bb = buffer_of(bias, bias != nullptr);
     for (int t = wave; t * 16 < N; t += kMlpWaves) {
         const int n0 = t * 16;
         const int nrow = n0 + l15 < N ? n0 + l15 : N - 1;
@@ -518,7 +526,10 @@ int launch_rows(MlpArgs &a, hipStream_t st)
     a.ldx = lds_stride(a.F), a.ldh = lds_stride(a.H), a.ldo = lds_stride(a.NH);
     const size_t lds = mlp_lds_bytes(a.F, a.H, a.NH, a.loss != MLP_LOSS_NONE);
     a.lds_floats = (int)(lds / 4) - kMlpWaves * 64;
-    if (lds > 160 * 1024) return fail(PPO_E_INVALID, "mlp_rows: a tile of %d features / %d hidden / %d heads needs %zu bytes of LDS", a.F, a.H, a.NH, lds);
+    // one rule for both entry points, the one ppo_mlp_supported answers by: a net whose training tile does not fit is
+    // refused by the inference launch as well, although its own tile is smaller
+    const size_t need = mlp_lds_bytes(a.F, a.H, a.NH, true);
+    if (need > 160 * 1024) return fail(PPO_E_INVALID, "mlp_rows: a tile of %d features / %d hidden / %d heads needs %zu bytes of LDS", a.F, a.H, a.NH, need);
     if (int rc = prepare_kernel<mlp_rows_kernel>("mlp_rows", 160 * 1024)) return rc;
     hipLaunchKernelGGL(mlp_rows_kernel, dim3((a.B + kRows - 1) / kRows), dim3(kMlpThreads), lds, st, a);
     return check_launch("mlp_rows_kernel");

@@ -22,12 +22,12 @@ import torch.nn.functional as F  # noqa: E402
 
 from ppo_amd import _lib, envs, logger, models, rollout  # noqa: E402
 from ppo_amd.config import args  # noqa: E402
+from mlp_float64_torch import LOG_SQRT_2PI, distil_loss_ref, gaussian_loss_ref, value_loss_ref  # noqa: E402
 
 HERE = os.path.dirname(__file__)
 GOLD = np.load(os.path.join(HERE, "golden", "variants_golden.npz"))
 META = json.load(open(os.path.join(HERE, "golden", "variants_golden.json")))
 DEV = "cuda"
-LOG_SQRT_2PI = 0.5 * math.log(2.0 * math.pi)
 
 
 def _p(t):
@@ -443,19 +443,6 @@ def within(got, ref, what, tol=1e-5):
     assert err <= tol * scale, f"{what}: max err {err:.3e} vs scale {scale:.3e}"
 
 
-def value_loss_ref(z, ret, tvf_ret, w, c, dt):
-    """include/ppo_amd.h, ppo_value_loss_f32: sum_i vf_coef (V_i - R_i)^2 + tvf_coef 0.5 sqrt(K) mean_k w_k (T_k - P_k)^2
-    per sample -> (d sum_b grad_scale loss_b / d heads, statistics [B, 4])."""
-    z = z.to(dt).requires_grad_(True)
-    V = z[:, c["value_col"]:c["value_col"] + c["vh"]]
-    P = z[:, c["tvf_col"]:c["tvf_col"] + c["K"] * c["stride"]:c["stride"]]
-    vloss = (c["vf_coef"] * (V - ret.to(dt)) ** 2).sum(1)
-    tloss = c["tvf_coef"] * 0.5 * math.sqrt(c["K"]) * (w.to(dt) * (tvf_ret.to(dt) - P) ** 2).mean(1)
-    (c["grad_scale"] * (vloss + tloss).sum()).backward()
-    stats = torch.stack([vloss, tloss, vloss + tloss, torch.zeros_like(vloss)], 1).detach()
-    return z.grad, stats
-
-
 VAL = dict(ldo=20, value_col=3, vh=2, tvf_col=6, K=5, stride=2, vf_coef=0.5, tvf_coef=0.7, grad_scale=0.37)
 
 
@@ -536,29 +523,6 @@ def test_value_loss_horizon_dropout_by_property():
     assert bool(((other[:, tv].double() - 2 * f).abs() <= 1e-5 * (2 * f).abs())[other_kept].all())
 
 
-def distil_loss_ref(z, targets, old, w, log_std, c, dt):
-    """include/ppo_amd.h, ppo_distil_loss_f32: 0.5 w_k (T_k - P_k)^2 [sqrt(n_pred) mean_k] + beta x policy term, the
-    policy term KL(new || old) on log-probabilities, or (log_std given) 2 x 0.5 mean_a (mu_old - mu)^2 / (1e-5 + 2
-    sigma_a^2) -> (d sum_b grad_scale loss_b / d heads, statistics [B, 4])."""
-    z = z.to(dt).requires_grad_(True)
-    nA, n = c["nA"], c["n_pred"]
-    P = z[:, c["pred_col"]:c["pred_col"] + n * c["stride"]:c["stride"]]
-    w = torch.ones(n, dtype=dt) if w is None else w.to(dt)
-    diff = P - targets.to(dt).reshape(-1, n)
-    vscale = math.sqrt(n) / n if c["vector"] else 1.0
-    vloss = (0.5 * vscale * w * diff ** 2).sum(1)
-    if log_std is None:
-        lp = F.log_softmax(z[:, :nA], dim=1)
-        pol = (lp.exp() * (lp - old.to(dt))).sum(1)
-    else:
-        den = 1e-5 + 2.0 * torch.exp(log_std.to(dt)) ** 2
-        pol = 2.0 * (0.5 * (old.to(dt) - z[:, :nA]) ** 2 / den).mean(1)
-    total = vloss + c["beta"] * pol
-    (c["grad_scale"] * total.sum()).backward()
-    stats = torch.stack([vloss, c["beta"] * pol, total, ((w * diff) ** 2).mean(1)], 1).detach()
-    return z.grad, stats
-
-
 def run_distil_loss(z, targets, old, w, log_std, idx, c):
     B = z.shape[0]
     dh = torch.full((B, c["ldo"]), float("nan"), device=DEV)
@@ -609,27 +573,6 @@ def test_distil_loss_index_against_float64(form, targets, B, factor):
 
 
 GAUSS = dict(ldo=9, nA=3, vh=2, eps=0.2, vf_coef=0.5, grad_scale=0.37)
-
-
-def gaussian_loss_ref(z, act, old, adv, ret, log_std, c, dt):
-    """include/ppo_amd.h, ppo_gaussian_loss_f32: gain_b = mean_a min(rho_a A, clip(rho_a) A) - sum_heads vf_coef (V - R)^2,
-    rho_a = exp(log N(a_a; mu_a, sigma_a) - old_log_pac_a); loss = -gain -> (d sum_b grad_scale loss_b / d heads,
-    the same per sample / d log_std [B, nA], statistics [B, 8], rho [B, nA])."""
-    z = z.to(dt).requires_grad_(True)
-    nA, vh, eps = c["nA"], c["vh"], c["eps"]
-    ls = log_std.to(dt).expand(z.shape[0], nA).clone().requires_grad_(True)  # one copy per sample: per-sample gradients
-    mu = z[:, :nA]
-    logpac = -((act.to(dt) - mu) ** 2) / (2.0 * torch.exp(ls) ** 2) - ls - LOG_SQRT_2PI
-    rho = torch.exp(logpac - old.to(dt))
-    A = adv.to(dt)[:, None]
-    loss_clip = torch.min(rho * A, torch.clamp(rho, 1 - eps, 1 + eps) * A).mean(1)
-    vloss = (c["vf_coef"] * (z[:, nA:nA + vh] - ret.to(dt)) ** 2).sum(1)
-    gain = loss_clip - vloss
-    (c["grad_scale"] * (-gain).sum()).backward()
-    zero = torch.zeros_like(gain)
-    stats = torch.stack([loss_clip, zero, vloss, (torch.abs(rho - 1.0) > eps).to(dt).mean(1),
-                         (old.to(dt) - logpac).mean(1), zero, gain, rho.mean(1)], 1).detach()
-    return z.grad, ls.grad, stats, rho.detach()
 
 
 def run_gaussian_loss(z, act, old, adv, ret, log_std, idx, c):
