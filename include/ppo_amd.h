@@ -261,6 +261,24 @@ int ppo_maxpool3x3s2_forward_f32(const float *in, float *out, uint8_t *argmax, i
 int ppo_maxpool3x3s2_backward_f32(const float *dout, const uint8_t *argmax, float *din, int n, int c, int h, int w,
                                   void *stream);
 
+/*
+ * 2x2 / stride 2 max pooling with the ReLU behind it in one launch (csrc/pool2x2.hip): the
+ * F.relu(torch.max_pool2d(., 2, 2)) behind every convolution of the RTG encoder (rl/models.py:203-205) and its
+ * autograd.  [n,c,h,w] -> [n,c,h/2,w/2]: the pool floors, a trailing odd row or column belongs to no window.  h and w
+ * always describe the PRE-pool map; out, dout and gate are [n,c,h/2,w/2].
+ * Forward: out = max(window, 0), a NaN in the window propagating.  gate (nullable uint8: an inference forward writes
+ *   nothing extra) records the winning tap ky*2+kx - the first maximum in row-major order, a NaN winning, as torch -
+ *   or 4 where the pooled value is not > 0 (the ReLU's derivative is 0 at 0).
+ * Backward: reads dout and gate only.  It writes EVERY element of din: dout at the recorded tap of a window whose
+ *   gate is below 4, zero at every other tap and in a trailing odd row or column.  Windows do not overlap: no atomics,
+ *   nothing for the caller to clear, exact.
+ * h < 2, w < 2, n < 1, c < 1, a null required pointer or a tensor of 2^30 elements or more: PPO_E_INVALID before any
+ * HIP call.  Any plane count: threads are indexed flat over (plane, window).
+ */
+int ppo_maxpool2x2_relu_forward_f32(const float *in, float *out, uint8_t *gate, int n, int c, int h, int w, void *stream);
+int ppo_maxpool2x2_relu_backward_f32(const float *dout, const uint8_t *gate, float *din, int n, int c, int h, int w,
+                                     void *stream);
+
 /* ------------------------------------------------------------------------
  * The same 3x3 / stride 1 / zero-padding 1 convolution at ANY geometry (csrc/conv3x3_any.hip): torch.nn.Conv2d as used
  * at rl/impala.py:61-62,96 and its autograd, for the observation shapes (--env_resolution, --env_color_mode,

@@ -44,6 +44,8 @@ SIGNATURES = {
     "ppo_conv3x3_backward_weight_f32": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _vp]),
     "ppo_maxpool3x3s2_forward_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "ppo_maxpool3x3s2_backward_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "ppo_maxpool2x2_relu_forward_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "ppo_maxpool2x2_relu_backward_f32": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "ppo_gemm_workspace_bytes": (_sz, [_i, _i, _i]),
     "ppo_gemm_f32": (_i, [_vp, _i64, _i64, _i, _vp, _i64, _i64, _i, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _sz, _vp]),
     "ppo_colsum_f32": (_i, [_vp, _i, _i, _i64, _vp, _i, _vp]),

@@ -71,9 +71,9 @@ class OptimizerConfig(_Group):  # rl/config.py:249-311
 class ModelConfig(_Group):  # rl/config.py:458-476
     FIELDS = (
         ("architecture", str, "dual", "[dual|single]  (north-star PPO = single)"),
-        ("encoder", str, "nature", "[nature|impala|mlp]"),
+        ("encoder", str, "nature", "[nature|impala|rtg|mlp]"),
         ("encoder_args", str, None, "dict of encoder arguments (impala: channels, n_block, down_sample [pool|stride|none]; "
-                                    "nature: base_channels)"),
+                                    "nature: base_channels; rtg: accepted and ignored)"),
         ("hidden_units", int, 256, "encoder output features"),
         ("head_scale", float, 0.1, "orthogonal-init gain of the heads"),
         ("head_bias", bool, True, "bias on the output heads"),

@@ -234,6 +234,34 @@ class NatureSpec:
         self.flat = c * h * w
 
 
+class RtgSpec:
+    """Static geometry of the RTG encoder (rl/models.py:172-213, RTG_LSTM - a plain CNN despite its name): conv 4x4
+    stride 2 without padding to 32 channels, then two 3x3 padding-1 convolutions (32 -> 64, 64 -> 64), each followed by
+    F.relu(max_pool2d(., 2, 2)) - the pool floors, so an odd last row or column is dropped - then a linear layer to
+    hidden_units.  Every other encoder argument is accepted and ignored, as the reference's **ignore_args does."""
+    kind = "rtg"
+
+    def __init__(self, input_dims, hidden_units=512, **ignored):
+        if len(input_dims) != 3:
+            raise ValueError(f"the rtg encoder takes [C, H, W] observations, got input_dims={input_dims}")
+        c, h, w = (int(d) for d in input_dims)
+        if h < 18 or w < 18:  # 18 -> 8 -> 4 -> 4 -> 2 -> 2 -> 1: three pools still leave one pixel
+            raise ValueError(f"input_dims={tuple(input_dims)} is too small for the rtg encoder (each side at least 18)")
+        if hidden_units < 1:
+            raise ValueError(f"the rtg encoder needs hidden_units >= 1, got {hidden_units}")
+        self.input_dims = (c, h, w)
+        self.hidden_units = hidden_units
+        # (name, cin, cout, kernel, stride, padding, h_in, w_in, h_conv, w_conv, h_pooled, w_pooled)
+        self.layers = []
+        for name, cout, k, s, p in (("conv1", 32, 4, 2, 0), ("conv2", 64, 3, 1, 1), ("conv3", 64, 3, 1, 1)):
+            hc, wc = (h + 2 * p - k) // s + 1, (w + 2 * p - k) // s + 1
+            self.layers.append((name, c, cout, k, s, p, h, w, hc, wc, hc // 2, wc // 2))
+            c, h, w = cout, hc // 2, wc // 2
+        self.pool_shapes = [(cout, hc, wc) for _n, _ci, cout, _k, _s, _p, _h, _w, hc, wc, _hp, _wp in self.layers]
+        self.out_shape = (c, h, w)
+        self.flat = c * h * w
+
+
 class MLPSpec:
     """StandardMLP (rl/models.py:148-169): fc1 -> tanh -> fc2 on a flat float observation."""
     kind = "mlp"
@@ -249,8 +277,17 @@ class MLPSpec:
 def init_encoder_parameters(spec):
     """Encoder parameters as CPU tensors, drawn from torch's global CPU generator in the reference's
     construction order (impala: rl/models.py:73-84, rl/impala.py:60-62, 96-100; mlp: rl/models.py:157-161;
-    nature: rl/models.py:114-125)."""
+    nature: rl/models.py:114-125; rtg: rl/models.py:183-194)."""
     init = OrderedDict()
+    if spec.kind == "rtg":
+        # plain nn.Conv2d / nn.Linear: torch's default initialisation (kaiming_uniform_(a=sqrt(5)) weights, uniform
+        # non-zero biases), tensors taken unchanged
+        for name, cin, cout, k, s, p, *_r in spec.layers:
+            m = torch.nn.Conv2d(cin, cout, kernel_size=k, stride=s, padding=p)
+            init[f"encoder.{name}.weight"], init[f"encoder.{name}.bias"] = m.weight.data, m.bias.data
+        m = torch.nn.Linear(spec.flat, spec.hidden_units)
+        init["encoder.fc.weight"], init["encoder.fc.bias"] = m.weight.data, m.bias.data
+        return init
     if spec.kind == "nature":
         for name, cin, cout, k, s, *_r in spec.layers:
             w, b = _custom_conv(cin, cout, k, s, scale=1.414)
@@ -412,8 +449,10 @@ class DualHeadNet:
 
     Encoders: ``impala`` (3x3 conv stacks, uint8 or float images; encoder arguments ``channels``, ``n_block`` and
     ``down_sample`` = 'pool' | 'stride' | 'none', see ImpalaSpec), ``nature`` (three strided convolutions and a linear
-    layer, uint8 or float images; op-by-op launches in exact float32 whatever `precision`) and ``mlp`` (flat float
-    observations);
+    layer, uint8 or float images; op-by-op launches in exact float32 whatever `precision`), ``rtg`` (a 4x4 stride-2 and
+    two 3x3 convolutions, each behind a fused 2x2 max-pool + ReLU launch, and a linear layer, torch's default
+    initialisation; uint8 or float images of at least 18x18, every encoder argument ignored; op-by-op in exact float32
+    like nature) and ``mlp`` (flat float observations);
     encoder activation ``relu`` (fused into the head GEMM's operand load) or ``tanh``.  All heads are ONE
     [nh, hidden] matrix so a forward is one GEMM: columns [policy nA | value VH | advantage nA | tvf K*VH].
     """
@@ -425,8 +464,8 @@ class DualHeadNet:
         encoder = encoder.lower()
         if precision not in ("low", "medium", "high"):
             raise ValueError(f"Invalid precision mode {precision}")
-        if encoder not in ("impala", "mlp", "nature"):
-            raise NotImplementedError(f"encoder '{encoder}' has no HIP path (impala | nature | mlp)")
+        if encoder not in ("impala", "mlp", "nature", "rtg"):
+            raise NotImplementedError(f"encoder '{encoder}' has no HIP path (impala | nature | rtg | mlp)")
         if activation_fn not in ("relu", "tanh"):
             raise ValueError(f"Invalid activation function {activation_fn}")
         _lib.require_gpu()
@@ -443,6 +482,13 @@ class DualHeadNet:
             for _name, cin, cout, k, s, h, w, _ho, _wo in self.spec.layers:
                 if not self.lib.ppo_conv2d_strided_supported(cin, cout, k, k, s, h, w):
                     raise _lib.PpoAmdError(f"no strided-convolution kernel for {cin}->{cout} {k}x{k}/{s} on {h}x{w}")
+        elif encoder == "rtg":
+            self.spec = RtgSpec(input_dims, hidden_units=hidden_units, **encoder_args)
+            for _name, cin, cout, k, s, p, h, w, *_r in self.spec.layers:
+                if p == 0 and not self.lib.ppo_conv2d_strided_supported(cin, cout, k, k, s, h, w):
+                    raise _lib.PpoAmdError(f"no strided-convolution kernel for {cin}->{cout} {k}x{k}/{s} on {h}x{w}")
+                if p == 1 and not self.lib.ppo_conv3x3_any_supported(cin, cout, h, w):
+                    raise _lib.PpoAmdError(f"no 3x3 convolution kernel for {cin}->{cout} on {h}x{w}")
         else:
             self.spec = MLPSpec(input_dims, hidden_units=hidden_units, **encoder_args)
         self.encoder_kind = encoder
@@ -918,6 +964,7 @@ class DualHeadNet:
                            _p(self.obs_norm.std), self.obs_norm.norm_eps, _p(x_in), x.shape[0], self.obs_norm.F)
             acts = (self._encode_mlp(x_in, train, tag) if self.encoder_kind == "mlp"
                     else self._encode_nature(x_in, train, tag, tail) if self.encoder_kind == "nature"
+                    else self._encode_rtg(x_in, train, tag, tail) if self.encoder_kind == "rtg"
                     else self._encode_impala(x_in, train, tag, index, tail, chain_split))
             acts.setdefault("tail_taken", False)  # (no dense + heads launch on this path)
             if self.encoder_activation_fn == "tanh" and "heads" not in acts:
@@ -968,6 +1015,30 @@ class DualHeadNet:
             acts[name] = y
             cur, mode = y, IN_NONE
         # conv3's output is already through its ReLU
+        return self._dense_heads(cur.view(B, sp.flat), 0, "encoder.fc", tag, train, acts, tail)
+
+    def _encode_rtg(self, x, train, tag, tail):
+        """RTG_LSTM.forward (rl/models.py:198-213), op by op: per layer the convolution without an activation (conv1 on the
+        strided kernel, conv2 and conv3 on the generic 3x3 one) and one launch for F.relu(max_pool2d(., 2, 2)), which in
+        a training forward also records the gate byte its backward reads; then the linear layer with the heads (and the
+        action step or the PPO loss) as behind the nature encoder.  Seven launches."""
+        sp, B = self.spec, x.shape[0]
+        acts = {"x": x}
+        cur, mode = x, (IN_U8 if x.dtype == torch.uint8 else IN_NONE)
+        for name, cin, cout, k, s, p, h, w, hc, wc, hp, wp in sp.layers:
+            y = self._buf(f"{tag}{name}", (B, cout, hc, wc))
+            wt, bias = self.params[f"encoder.{name}.weight"], self.params[f"encoder.{name}.bias"]
+            if p == 0:
+                self._call("ppo_conv2d_strided_forward_f32", _p(cur), mode, _p(wt), _p(bias), _p(y), 0, B, cin, h, w, cout,
+                           k, k, s)
+            else:
+                self._call("ppo_conv3x3_any_forward_f32", _p(cur), mode, _p(wt), _p(bias), None, _p(y), B, cin, cout, h, w)
+            q = self._buf(f"{tag}{name}_pool", (B, cout, hp, wp))
+            gate = self._buf(f"{tag}{name}_gate", (B, cout, hp, wp), torch.uint8) if train else None
+            self._call("ppo_maxpool2x2_relu_forward_f32", _p(y), _p(q), _p(gate), B, cout, hc, wc)
+            acts[name], acts[name + "_gate"] = q, gate
+            cur, mode = q, IN_NONE
+        # the last pooled map is already through its ReLU
         return self._dense_heads(cur.view(B, sp.flat), 0, "encoder.fc", tag, train, acts, tail)
 
     def _dense_heads(self, flat, relu_x, wname, tag, train, acts, tail):
@@ -1324,6 +1395,8 @@ class DualHeadNet:
             self._backward_mlp(acts, dh)
         elif self.encoder_kind == "nature":
             self._backward_nature(acts, dh)
+        elif self.encoder_kind == "rtg":
+            self._backward_rtg(acts, dh)
         else:
             self._backward_impala(acts, dh, dense_bias_done)
 
@@ -1360,6 +1433,42 @@ class DualHeadNet:
                 self._call("ppo_conv2d_strided_backward_data_f32", _p(g), _p(gate), _p(self.params[f"encoder.{name}.weight"]),
                            _p(gx), *geom)
                 g, gate = gx, src
+        if self.grad_ready_hook is not None:
+            self.grad_ready_hook(torch.cuda.current_stream())
+
+    def _backward_rtg(self, acts, dh):
+        """Backward through the RTG encoder, one launch per gradient: the linear layer (its data gradient unmasked - the
+        pool backward applies the gate, which holds the ReLU's decision too), then per layer from the last the pool +
+        ReLU backward into the pre-pool map, the weight and bias gradient, and the data gradient where a layer lies
+        below - nothing back-propagates into the observations."""
+        sp = self.spec
+        B = dh.shape[0]
+        x, flat = acts["x"], acts["flat"]
+        g = self._buf("rg_conv3_pool", tuple(acts["conv3"].shape))
+        self._linear_backward(flat, sp.flat, "encoder.fc", dh, g.view(B, sp.flat))
+        for li in (2, 1, 0):
+            name, cin, cout, k, s, p, h, w, hc, wc, _hp, _wp = sp.layers[li]
+            src = acts[sp.layers[li - 1][0]] if li else x
+            mode = IN_U8 if src.dtype == torch.uint8 else IN_NONE
+            dy = self._buf("rg_" + name, (B, cout, hc, wc))
+            self._call("ppo_maxpool2x2_relu_backward_f32", _p(g), _p(acts[name + "_gate"]), _p(dy), B, cout, hc, wc)
+            dw, db = self.grads[f"encoder.{name}.weight"], self.grads[f"encoder.{name}.bias"]
+            if p == 0:
+                geom = (B, cin, h, w, cout, k, k, s)
+                nbytes = int(self.lib.ppo_conv2d_strided_wgrad_workspace_bytes(*geom))
+                ws = self._ws("rwgrad_ws_" + name, nbytes)
+                self._call("ppo_conv2d_strided_backward_weight_f32", _p(src), mode, _p(dy), None, _p(dw), _p(db), _p(ws),
+                           nbytes, *geom)
+            else:
+                nbytes = int(self.lib.ppo_conv3x3_any_wgrad_workspace_bytes(B, cin, cout, h, w))
+                ws = self._ws("rwgrad_ws_" + name, nbytes)
+                self._call("ppo_conv3x3_any_backward_weight_f32", _p(src), mode, _p(dy), _p(dw), _p(db), _p(ws), nbytes,
+                           B, cin, cout, h, w, 0)
+            if li:
+                gx = self._buf("rg_" + sp.layers[li - 1][0] + "_pool", tuple(src.shape))
+                self._call("ppo_conv3x3_any_backward_data_f32", _p(dy), _p(self.params[f"encoder.{name}.weight"]), None, None,
+                           _p(gx), B, cin, cout, h, w)
+                g = gx
         if self.grad_ready_hook is not None:
             self.grad_ready_hook(torch.cuda.current_stream())
 
@@ -1659,7 +1768,7 @@ class DualHeadNet:
         (ppo_conv3x3_pool_forward_packed_indexed_f32 + the indexed first-layer weight gradient) instead of from a
         gathered copy: uint8 images into the fused first convolution + max-pool, the pooled-gradient weight-gradient form.
         IMPALA only, and only where the first convolution has its specialised kernels (the generic ones take the gathered
-        minibatch): the nature and mlp op-by-op paths take the gathered minibatch."""
+        minibatch): the nature, rtg and mlp op-by-op paths take the gathered minibatch."""
         if self.encoder_kind != "impala" or "encoder.stacks.0.firstconv" in self._generic or obs.dtype != torch.uint8 \
                 or self.obs_norm is not None or not GATHER_IN_CONV or self.spec.down_sample != "pool":
             return False

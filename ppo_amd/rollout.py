@@ -135,7 +135,7 @@ class Runner:
         self._tvf_subset_weight_cache = {}
         N, A, nA, VH, dev = self.N, self.A, self.n_actions, self.VH, self.device
         gaussian = action_dist == "gaussian"
-        obs_dtype = torch.uint8 if model.policy_net.encoder_kind in ("impala", "nature") and args.env.type != "mujoco" else torch.float32
+        obs_dtype = torch.uint8 if model.policy_net.encoder_kind in ("impala", "nature", "rtg") and args.env.type != "mujoco" else torch.float32
         # ---- rollout buffers, all resident in HBM (time-major, env index contiguous)
         self.all_obs = torch.zeros((N + 1, A, *self.state_shape), dtype=obs_dtype, device=dev)
         self.value = torch.zeros((N + 1, A, VH), dtype=torch.float32, device=dev)
