@@ -1077,6 +1077,55 @@ int ppo_conv3x3_pack_bf16_split(const float *weight, void *packed, int cin, int 
 int ppo_conv3x3_bf16_split(const float *in, int relu_in, const void *packed, const float *bias, float *out, int n, int cin, int cout,
                            int h, int w, int n_split, void *stream);
 
+/* ------------------------------------------------------------------------
+ * Batch normalisation of the IMPALA residual blocks (csrc/batchnorm.hip).  Reference: bn0 / bn1 of CnnBasicBlock,
+ * rl/impala.py:63-76, each an nn.BatchNorm2d(C) with torch's defaults - eps 1e-5, momentum 0.1, affine, running
+ * statistics tracked.  Maps are NCHW float32, contiguous, any n, c, h, w >= 1 (c <= 65535); planes need no alignment, and
+ * 16-byte aligned base pointers take the vectorised path.  Every launch writes z = s*x + t per channel WITHOUT a ReLU: the
+ * convolution that follows reads it with PPO_IN_RELU.  All sums over n*h*w run in float64 in an order fixed by the shape,
+ * without atomics: results are bit-identical from run to run.  s and t are formed in float64 and rounded once.
+ * workspace: ppo_batchnorm_workspace_bytes(c) bytes, 8-byte aligned, scratch between the two launches of a call.
+ * ---------------------------------------------------------------------- */
+#define PPO_BATCHNORM_MAX_SLICES 64 /* workgroups that share one channel's sums */
+size_t ppo_batchnorm_workspace_bytes(int c);
+
+/*
+ * nn.BatchNorm2d.forward in train mode (rl/impala.py:63-76 under model.train(), i.e. during generate_rollout,
+ * rl/rollout.py:712): two launches.
+ *   mean_c = sum x / m,  var_c = sum x^2 / m - mean_c^2 (biased),  m = n*h*w >= 2
+ *   s = gamma / sqrt(var + eps),  t = beta - mean * s,  z = s*x + t
+ *   running_mean = (1 - momentum) * running_mean + momentum * mean
+ *   running_var  = (1 - momentum) * running_var  + momentum * var * m / (m - 1)      (the unbiased estimate)
+ *   num_batches_tracked += 1                                                         (device int64)
+ * running_mean, running_var, num_batches_tracked, batch_mean, batch_var ([c] each) are nullable; the last two receive
+ * the statistics the normalisation used.  There is no backward pass of this form: the reference never runs one.
+ */
+int ppo_batchnorm_batch_forward_f32(const float *x, const float *gamma, const float *beta, float *running_mean,
+                                    float *running_var, int64_t *num_batches_tracked, float *z, float *batch_mean,
+                                    float *batch_var, void *workspace, size_t workspace_bytes, int n, int c, int h, int w,
+                                    double eps, double momentum, void *stream);
+
+/*
+ * nn.BatchNorm2d.forward in eval mode (rl/impala.py:63-76 after model.eval(), rl/rollout.py:927, 1192, 2228): one launch,
+ *   s = gamma / sqrt(running_var + eps),  t = beta - running_mean * s,  z = s*x + t.
+ */
+int ppo_batchnorm_running_forward_f32(const float *x, const float *gamma, const float *beta, const float *running_mean,
+                                      const float *running_var, float *z, int n, int c, int h, int w, double eps,
+                                      void *stream);
+
+/*
+ * Backward of the eval-mode layer (rl/impala.py:63-76 inside a minibatch update; the running statistics are constants):
+ *   dx = s * dz (+ residual)
+ *   dgamma_c = sum dz * (x - running_mean_c) / sqrt(running_var_c + eps),   dbeta_c = sum dz
+ * dz: gradient w.r.t. z, already masked by the following convolution's backward-data (relu_src = z).  x: the layer's
+ * input.  residual (nullable): a gradient added to dx - for bn0 the block's output gradient arriving over the skip.
+ * accumulate != 0 adds to dgamma / dbeta (micro-batches), otherwise they are overwritten.  Two launches.
+ */
+int ppo_batchnorm_running_backward_f32(const float *dz, const float *x, const float *residual, const float *gamma,
+                                       const float *running_mean, const float *running_var, float *dx, float *dgamma,
+                                       float *dbeta, void *workspace, size_t workspace_bytes, int n, int c, int h, int w,
+                                       double eps, int accumulate, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -177,6 +177,10 @@ SIGNATURES = {
     "ppo_grad_noise_workspace_bytes": (_sz, [_i]),
     "ppo_grad_noise_pass_f32": (_i, [_vp, _vp, _i64, _i, _i, _vp, _vp]),
     "ppo_grad_noise_finish_f64": (_i, [_vp, _i64, _i, _i, _vp, _vp, _vp]),
+    "ppo_batchnorm_workspace_bytes": (_sz, [_i]),
+    "ppo_batchnorm_batch_forward_f32": (_i, [_vp] * 10 + [_sz, _i, _i, _i, _i, _d, _d, _vp]),
+    "ppo_batchnorm_running_forward_f32": (_i, [_vp] * 6 + [_i, _i, _i, _i, _d, _vp]),
+    "ppo_batchnorm_running_backward_f32": (_i, [_vp] * 10 + [_sz, _i, _i, _i, _i, _d, _i, _vp]),
 }
 
 class PackJob(ctypes.Structure):

@@ -72,7 +72,9 @@ class ModelConfig(_Group):  # rl/config.py:458-476
     FIELDS = (
         ("architecture", str, "dual", "[dual|single]  (north-star PPO = single)"),
         ("encoder", str, "nature", "[nature|impala|rtg|mlp]"),
-        ("encoder_args", str, None, "dict of encoder arguments (impala: channels, n_block, down_sample [pool|stride|none]; "
+        ("encoder_args", str, None, "dict of encoder arguments (impala: channels, n_block, down_sample [pool|stride|none], "
+                                    "batch_norm [True: bn0 / bn1 in every residual block, batch statistics during the "
+                                    "rollout, running statistics everywhere else; one GPU]; "
                                     "nature: base_channels; rtg: accepted and ignored)"),
         ("hidden_units", int, 256, "encoder output features"),
         ("head_scale", float, 0.1, "orthogonal-init gain of the heads"),

@@ -110,6 +110,7 @@ FUSE_MLP = int(os.environ.get("PPO_AMD_FUSE_MLP", "1"))
 # its weight gradient) instead of being gathered into a second buffer by a launch of its own (0 = gather first)
 GATHER_IN_CONV = int(os.environ.get("PPO_AMD_GATHER_IN_CONV", "1"))
 HEAD_NAMES = ("policy_head", "value_head", "advantage_head", "tvf_head")
+BN_EPS, BN_MOMENTUM = 1e-5, 0.1  # nn.BatchNorm2d's defaults, which rl/impala.py:64-65 takes
 
 
 def _p(t):
@@ -191,7 +192,9 @@ class ImpalaSpec:
         if down_sample not in ("pool", "stride", "none"):
             raise ValueError(f"Invalid down_sample mode {down_sample}")  # rl/impala.py:123
         if batch_norm:
-            raise NotImplementedError("batch_norm=True: the IMPALA encoder's batch-norm layers have no HIP path")
+            # the spec is the static geometry, which batch norm does not change: the layers are DualHeadNet's
+            raise NotImplementedError("batch_norm is not an argument of ImpalaSpec: pass batch_norm=True to DualHeadNet "
+                                      "(or in --model_encoder_args), which builds the batch-norm layers itself")
         c, h, w = input_dims
         self.input_dims = tuple(input_dims)
         self.channels = tuple(channels)
@@ -274,10 +277,12 @@ class MLPSpec:
         self.hidden_units = hidden_units
 
 
-def init_encoder_parameters(spec):
+def init_encoder_parameters(spec, batch_norm=False):
     """Encoder parameters as CPU tensors, drawn from torch's global CPU generator in the reference's
     construction order (impala: rl/models.py:73-84, rl/impala.py:60-62, 96-100; mlp: rl/models.py:157-161;
-    nature: rl/models.py:114-125; rtg: rl/models.py:183-194)."""
+    nature: rl/models.py:114-125; rtg: rl/models.py:183-194).  `batch_norm` (impala): every residual block also has
+    bn0 / bn1 (rl/impala.py:63-65) behind its convolutions, as the reference's named_parameters() lists them - weight
+    (gamma) ones, bias (beta) zeros; nn.BatchNorm2d draws nothing, so every other tensor is what it is without."""
     init = OrderedDict()
     if spec.kind == "rtg":
         # plain nn.Conv2d / nn.Linear: torch's default initialisation (kaiming_uniform_(a=sqrt(5)) weights, uniform
@@ -311,17 +316,21 @@ def init_encoder_parameters(spec):
                 w, b = _normed_conv(cout, cout, scale=s_block)
                 init[f"encoder.stacks.{si}.blocks.{bi}.{cname}.weight"] = w
                 init[f"encoder.stacks.{si}.blocks.{bi}.{cname}.bias"] = b
+            for bname in (("bn0", "bn1") if batch_norm else ()):
+                init[f"encoder.stacks.{si}.blocks.{bi}.{bname}.weight"] = torch.ones(cout)
+                init[f"encoder.stacks.{si}.blocks.{bi}.{bname}.bias"] = torch.zeros(cout)
     w, b = _normed_linear(spec.flat, spec.hidden_units, scale=1.414)  # rl/models.py:84
     init["encoder.dense.weight"], init["encoder.dense.bias"] = w, b
     return init
 
 
-def init_parameters(spec, n_actions: int, vh: int, head_scale: float, head_bias: bool, n_tvf: int = 0):
+def init_parameters(spec, n_actions: int, vh: int, head_scale: float, head_bias: bool, n_tvf: int = 0,
+                    batch_norm: bool = False):
     """Initial parameters of DualHeadNet as CPU tensors in the reference's construction order
     (rl/models.py:348-384: encoder, policy / value / advantage heads, log_std, then the TVF head), so
     that the same ``torch.manual_seed`` reproduces the reference's initial weights exactly.
     Keys are the reference's names relative to ``policy_net``."""
-    init = init_encoder_parameters(spec)
+    init = init_encoder_parameters(spec, batch_norm=batch_norm)
     heads = [("policy_head", n_actions), ("value_head", vh), ("advantage_head", n_actions)]
     if n_tvf:
         heads.append(("tvf_head", n_tvf * vh))
@@ -332,6 +341,26 @@ def init_parameters(spec, n_actions: int, vh: int, head_scale: float, head_bias:
             init[f"{name}.bias"] = b
     init["log_std"] = torch.zeros(n_actions)  # rl/models.py:368 (no random draw, so its position is free)
     return init
+
+
+BN_BUFFERS = ("running_mean", "running_var", "num_batches_tracked")
+
+
+def is_bn_buffer(name: str) -> bool:
+    return name.rsplit(".", 1)[-1] in BN_BUFFERS
+
+
+def state_dict_names(init_names, batch_norm: bool = False):
+    """The keys of the reference module's state_dict() for the names init_parameters returns: log_std first (a parameter
+    of the net itself, ahead of its sub-modules), then construction order, with nn.BatchNorm2d's buffers behind their
+    layer's weight and bias.  Without the buffers (is_bn_buffer) it is the order of named_parameters(), which the integer
+    keys of torch.optim.Adam's state dict index."""
+    names = []
+    for n in ["log_std"] + [n for n in init_names if n != "log_std"]:
+        names.append(n)
+        if batch_norm and n.endswith(".bias") and n.split(".")[-2] in ("bn0", "bn1"):
+            names += [n[:-len("bias")] + b for b in BN_BUFFERS]
+    return names
 
 
 def init_impala_parameters(spec: ImpalaSpec, n_actions: int, vh: int, head_scale: float, head_bias: bool):
@@ -448,7 +477,8 @@ class DualHeadNet:
     """One encoder + policy / value / advantage (/ TVF) heads (reference: rl/models.py:304-508), HIP-backed.
 
     Encoders: ``impala`` (3x3 conv stacks, uint8 or float images; encoder arguments ``channels``, ``n_block`` and
-    ``down_sample`` = 'pool' | 'stride' | 'none', see ImpalaSpec), ``nature`` (three strided convolutions and a linear
+    ``down_sample`` = 'pool' | 'stride' | 'none', see ImpalaSpec, and ``batch_norm``: bn0 / bn1 in every residual block,
+    op-by-op launches in exact float32, the mode switched by train() / eval() - see `training`), ``nature`` (three strided convolutions and a linear
     layer, uint8 or float images; op-by-op launches in exact float32 whatever `precision`), ``rtg`` (a 4x4 stride-2 and
     two 3x3 convolutions, each behind a fused 2x2 max-pool + ReLU launch, and a linear layer, torch's default
     initialisation; uint8 or float images of at least 18x18, every encoder argument ignored; op-by-op in exact float32
@@ -475,6 +505,12 @@ class DualHeadNet:
             raise _lib.PpoAmdError(f"device '{device}': the HIP path runs on the GPU only")
         if self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
+        # batch_norm=True (impala only): bn0 / bn1 in every residual block (rl/impala.py:63-76), see _encode_impala_bn
+        self.batch_norm = bool(encoder_args.pop("batch_norm", False)) if encoder == "impala" else False
+        # nn.Module.training.  Only a batch-norm net reads it: set, an inference forward normalises with the statistics of
+        # its own batch and updates the running ones (the rollout, rl/rollout.py:712); cleared, every forward uses the
+        # running statistics (rl/rollout.py:927, 1192, 2228).  Not encode()'s `train` argument - see there.
+        self.training = True
         if encoder == "impala":
             self.spec = ImpalaSpec(input_dims, hidden_units=hidden_units, **encoder_args)
         elif encoder == "nature":
@@ -516,7 +552,7 @@ class DualHeadNet:
         self.obs_norm = None  # shared ObsNormalizer (set by TVFModel when observation_normalization is on)
         self.grad_ready_hook = None  # callable(stream), see _backward_impala (data-parallel gradient buckets)
         self._split_ws = {}  # workspaces of the two-workgroups-per-image chain launch
-        self._plans = {}   # (tag, batch, dtype, chain_split) -> recorded inference launch list
+        self._plans = {}   # (tag, batch, dtype, chain_split[, training: batch-norm nets]) -> recorded inference launch list
         self.use_plans = True  # False: every inference launch goes through _call (bench.py's per-kernel table brackets it)
         self._find_generic_convs()
         self._build_packed_weights()
@@ -533,7 +569,15 @@ class DualHeadNet:
     # ------------------------------------------------------------------ parameters
     def _build_parameters(self, head_scale):
         sp = self.spec
-        init = init_parameters(sp, self.n_actions, self.vh, head_scale, self.head_bias, self.K)
+        init = init_parameters(sp, self.n_actions, self.vh, head_scale, self.head_bias, self.K, batch_norm=self.batch_norm)
+        # nn.BatchNorm2d's buffers, outside the flat parameter buffer (no optimiser, gradient or reducer sees them):
+        # name -> tensor in state_dict order, behind their layer's weight and bias
+        self.buffers = OrderedDict()
+        for name in state_dict_names(init.keys(), self.batch_norm):
+            if is_bn_buffer(name):
+                c = init[name.rsplit(".", 1)[0] + ".bias"].numel()
+                self.buffers[name] = (torch.zeros((), dtype=torch.int64, device=self.device) if name.endswith("tracked")
+                                      else torch.full((c,), float(name.endswith("var")), dtype=torch.float32, device=self.device))
         # physical order: encoder..., then the head weights contiguous (one [nh, hidden] matrix),
         # then the head biases contiguous, then log_std
         head_names = [n for n in HEAD_NAMES if f"{n}.weight" in init]
@@ -580,8 +624,8 @@ class DualHeadNet:
         its four block convolutions, refreshed by ONE launch behind the float32 re-pack."""
         self.precision = precision
         self.split_bf16, self._pk16, self._split_jobs, self._split_conv_jobs = False, {}, None, None
-        if precision == "high" or self.encoder_kind != "impala" or self.spec.n_block != 2:
-            return
+        if precision == "high" or self.encoder_kind != "impala" or self.spec.n_block != 2 or self.batch_norm:
+            return  # (a batch-norm net runs op by op in exact float32 whatever `precision`, like nature and rtg)
         jobs = []
         nbytes = int(self.lib.ppo_impala_stack_tail_bf16x3_packed_bytes())
         for si, (_cin, cout, _h, _w, ho, wo) in enumerate(self.spec.stacks):
@@ -701,9 +745,19 @@ class DualHeadNet:
         return sum(int(np.prod(s)) for _, s in self._offsets.values())
 
     def state_dict(self) -> "OrderedDict[str, torch.Tensor]":
-        """Reference key names (policy_net.<these>), tensors are views into the flat buffer."""
-        names = ["log_std"] + [n for n in self._state_order if n != "log_std"]
-        return OrderedDict((n, self.params[n]) for n in names)
+        """Reference key names (policy_net.<these>), tensors are views into the flat buffer - and, on a batch-norm net,
+        the layers' buffers (running_mean, running_var, num_batches_tracked) behind each layer's weight and bias, where
+        nn.Module.state_dict() puts them."""
+        return OrderedDict((n, self.params[n] if n in self.params else self.buffers[n])
+                           for n in state_dict_names(self._state_order, self.batch_norm))
+
+    def train(self, mode: bool = True):
+        """nn.Module.train: see `training` (__init__)."""
+        self.training = bool(mode)
+        return self
+
+    def eval(self):
+        return self.train(False)
 
     # ------------------------------------------------------------------ convolutions without a specialised kernel
     def _find_generic_convs(self):
@@ -762,8 +816,9 @@ class DualHeadNet:
             return
         jobs, total = [], 0
         for name, w in self.params.items():
-            if not (name.startswith("encoder.stacks.") and name.endswith(".weight")) or name[:-len(".weight")] in self._generic:
-                continue  # (the generic kernels read the raw tensor)
+            if not (name.startswith("encoder.stacks.") and name.endswith(".weight")) or name[:-len(".weight")] in self._generic \
+                    or w.dim() != 4:
+                continue  # (the generic kernels read the raw tensor; a batch-norm layer's weight is no convolution's)
             cout, cin = int(w.shape[0]), int(w.shape[1])
             for transposed in (0, 1):
                 if transposed and name == "encoder.stacks.0.firstconv.weight":
@@ -826,14 +881,17 @@ class DualHeadNet:
 
     def load_state_dict(self, sd, strict=True):
         self.mark_weights_changed()
-        missing = [n for n in self.params if n not in sd]
-        unexpected = [n for n in sd if n not in self.params]
+        missing = [n for n in (*self.params, *self.buffers) if n not in sd]
+        unexpected = [n for n in sd if n not in self.params and n not in self.buffers]
         if strict and (missing or unexpected):
             raise KeyError(f"state_dict mismatch: missing {missing}, unexpected {unexpected}")
         with torch.no_grad():
             for n, t in sd.items():
                 if n in self.params:
                     self.params[n].copy_(torch.as_tensor(t).to(self.device, torch.float32).reshape(self.params[n].shape))
+                elif n in self.buffers:  # in place: recorded launch plans hold their addresses
+                    b = self.buffers[n]
+                    b.copy_(torch.as_tensor(t).to(self.device, b.dtype).reshape(b.shape))
         self.mask_feature_weights()
 
     # ------------------------------------------------------------------ scratch memory
@@ -932,6 +990,15 @@ class DualHeadNet:
         # persist, parameters are views of one flat buffer — except the input, which is patched in.  That cuts
         # the per-launch Python work to the ctypes call itself.
         key = (tag, x.shape[0], x.dtype, chain_split)
+        if self.batch_norm:
+            # Two flags meet here.  `train` (this call): keep the maps for a backward pass.  `self.training` (the net, as
+            # nn.Module's): normalise with batch statistics and update the running ones.  A batch-norm net records its
+            # two modes as different plans - they are different launches - and a replayed batch-statistics plan updates
+            # the running statistics exactly as the recorded one did: the launches write them.
+            if train and self.training:
+                raise RuntimeError("a training forward of a batch-norm net in training mode: back-propagation through "
+                                   "batch statistics is not built (and the reference never runs it) - call eval() first")
+            key += (self.training,)
         plan = None if train or not self.use_plans else self._plans.get(key)
         if plan is not None:
             calls, acts, x_slots, heads_at = plan
@@ -965,6 +1032,7 @@ class DualHeadNet:
             acts = (self._encode_mlp(x_in, train, tag) if self.encoder_kind == "mlp"
                     else self._encode_nature(x_in, train, tag, tail) if self.encoder_kind == "nature"
                     else self._encode_rtg(x_in, train, tag, tail) if self.encoder_kind == "rtg"
+                    else self._encode_impala_bn(x_in, train, tag, tail) if self.batch_norm
                     else self._encode_impala(x_in, train, tag, index, tail, chain_split))
             acts.setdefault("tail_taken", False)  # (no dense + heads launch on this path)
             if self.encoder_activation_fn == "tanh" and "heads" not in acts:
@@ -1040,6 +1108,57 @@ class DualHeadNet:
             cur, mode = q, IN_NONE
         # the last pooled map is already through its ReLU
         return self._dense_heads(cur.view(B, sp.flat), 0, "encoder.fc", tag, train, acts, tail)
+
+    def _batchnorm(self, x, base, z, tag, n, c, h, w):
+        """z = bn(x) for layer `base` (…blocks.k.bn0 | bn1; nn.BatchNorm2d defaults, rl/impala.py:63-76) WITHOUT the ReLU -
+        the next convolution reads z with IN_RELU.  In training mode two launches that use this batch's statistics and
+        update the layer's buffers, otherwise one launch on the running statistics."""
+        gamma, beta = self.params[base + ".weight"], self.params[base + ".bias"]
+        rm, rv = self.buffers[base + ".running_mean"], self.buffers[base + ".running_var"]
+        if self.training:
+            nbytes = int(self.lib.ppo_batchnorm_workspace_bytes(c))
+            ws = self._buf(f"{tag}bn_ws", ((nbytes + 7) // 8,), torch.float64)
+            self._call("ppo_batchnorm_batch_forward_f32", _p(x), _p(gamma), _p(beta), _p(rm), _p(rv),
+                       _p(self.buffers[base + ".num_batches_tracked"]), _p(z), None, None, _p(ws), nbytes, n, c, h, w,
+                       BN_EPS, BN_MOMENTUM)
+        else:
+            self._call("ppo_batchnorm_running_forward_f32", _p(x), _p(gamma), _p(beta), _p(rm), _p(rv), _p(z), n, c, h, w, BN_EPS)
+
+    def _encode_impala_bn(self, x, train, tag, tail):
+        """The IMPALA encoder with batch_norm=True (rl/impala.py:67-108), op by op in exact float32: per stack the first
+        convolution with its pool or stride through the single-operation entry points, then per residual block
+        z0 = bn0(q); a = conv0(relu(z0)); z1 = bn1(a); q' = q + conv1(relu(z1)) as batch-norm launch, convolution,
+        batch-norm launch, convolution with the skip as residual.  No whole-stack, block-fused or split-bf16 launch."""
+        sp, B = self.spec, x.shape[0]
+        acts = {"x": x}
+        cur, cur_mode = x, (IN_U8 if x.dtype == torch.uint8 else IN_NONE)
+        for si, (cin, cout, h, w, ho, wo) in enumerate(sp.stacks):
+            wname = f"encoder.stacks.{si}.firstconv"
+            p = self._buf(f"{tag}p{si}", (B, cout, ho, wo))
+            idx = None
+            if sp.down_sample == "pool":
+                idx = self._buf(f"{tag}idx{si}", (B, cout, ho, wo), torch.uint8) if train else None
+                c = self._buf(f"{tag}c{si}", (B, cout, h, w))
+                self._conv(cur, cur_mode, wname, c, None, B, cin, cout, h, w)
+                self._call("ppo_maxpool3x3s2_forward_f32", _p(c), _p(p), _p(idx), B, cout, h, w)
+            elif sp.down_sample == "stride":
+                self._call("ppo_conv3x3s2_any_forward_f32", _p(cur), cur_mode, _p(self.params[wname + ".weight"]),
+                           _p(self.params[wname + ".bias"]), None, _p(p), B, cin, cout, h, w)
+            else:
+                self._conv(cur, cur_mode, wname, p, None, B, cin, cout, h, w)
+            acts[f"in{si}"], acts[f"idx{si}"] = cur, idx
+            q = p
+            for bi in range(sp.n_block):
+                base = f"encoder.stacks.{si}.blocks.{bi}"
+                z0, a, z1, qn = (self._buf(f"{tag}{k}{si}_{bi}", (B, cout, ho, wo)) for k in ("z0_", "a", "z1_", "q"))
+                self._batchnorm(q, base + ".bn0", z0, tag, B, cout, ho, wo)
+                self._conv(z0, IN_RELU, base + ".conv0", a, None, B, cout, cout, ho, wo)
+                self._batchnorm(a, base + ".bn1", z1, tag, B, cout, ho, wo)
+                self._conv(z1, IN_RELU, base + ".conv1", qn, q, B, cout, cout, ho, wo)
+                acts[f"q{si}_{bi}_in"], acts[f"z0_{si}_{bi}"], acts[f"a{si}_{bi}"], acts[f"z1_{si}_{bi}"] = q, z0, a, z1
+                q = qn
+            cur, cur_mode = q, IN_NONE
+        return self._dense_heads(cur.view(B, sp.flat), 1, "encoder.dense", tag, train, acts, tail)
 
     def _dense_heads(self, flat, relu_x, wname, tag, train, acts, tail):
         """The encoder's last linear layer `wname` on relu(flat) (relu_x = 1) or flat (0), and - where the encoder
@@ -1130,7 +1249,8 @@ class DualHeadNet:
 
     def chain_split_armed(self) -> bool:
         """Whether a forward with chain_split=True may take the split launch (so its caller has to check for errors)."""
-        return bool(CHAIN_SPLIT) and self.encoder_kind == "impala" and self._chain_split_usable is not False
+        return bool(CHAIN_SPLIT) and self.encoder_kind == "impala" and not self.batch_norm \
+            and self._chain_split_usable is not False
 
     def chain_split_disable(self):
         """After an error: the one-workgroup launch from now on.  Clears the error (and fault-injection) words and
@@ -1397,6 +1517,8 @@ class DualHeadNet:
             self._backward_nature(acts, dh)
         elif self.encoder_kind == "rtg":
             self._backward_rtg(acts, dh)
+        elif self.batch_norm:
+            self._backward_impala_bn(acts, dh, dense_bias_done)
         else:
             self._backward_impala(acts, dh, dense_bias_done)
 
@@ -1471,6 +1593,82 @@ class DualHeadNet:
                 g = gx
         if self.grad_ready_hook is not None:
             self.grad_ready_hook(torch.cuda.current_stream())
+
+    def _backward_impala_bn(self, acts, dh, dense_bias_done=False):
+        """Backward through the batch-norm IMPALA encoder (eval mode: every bn is a per-channel affine map of constants
+        s = gamma / sqrt(running_var + eps), t = beta - running_mean * s), one launch per gradient.  Per block, from
+        g = d loss / d (block output), with out = q + conv1(relu(z1)), z1 = bn1(a), a = conv0(relu(z0)), z0 = bn0(q):
+        conv1's weight gradient, its data gradient gated by z1, bn1's backward (dgamma, dbeta, da), conv0's weight
+        gradient, its data gradient gated by z0, and bn0's backward, which takes g - the skip - as its residual.  Then
+        the max-pool backward (down_sample 'pool') and the stack's first convolution."""
+        sp, lib = self.spec, self.lib
+        B = dh.shape[0]
+        flat = acts["flat"]
+        c_last, h_last, w_last = sp.out_shape
+        g = self._buf(f"g{len(sp.stacks) - 1}_top", (B, c_last, h_last, w_last))
+        self._linear_backward(flat, sp.flat, "encoder.dense", dh, g, relu_x=1, mask=flat, bias_done=dense_bias_done)
+        if self.grad_ready_hook is not None:
+            self.grad_ready_hook(torch.cuda.current_stream())
+
+        def wgrad(x, mode, dy, wname, cin, cout, hh, ww):
+            dw, db = self.grads[wname + ".weight"], self.grads[wname + ".bias"]
+            if wname in self._generic:
+                nbytes = int(lib.ppo_conv3x3_any_wgrad_workspace_bytes(B, cin, cout, hh, ww))
+                fn = "ppo_conv3x3_any_backward_weight_f32"
+            else:
+                nbytes = int(lib.ppo_conv3x3_wgrad_workspace_bytes(cin, cout))
+                fn = "ppo_conv3x3_backward_weight_f32"
+            ws = self._ws("wgrad_ws_" + wname, nbytes)
+            self._call(fn, _p(x), mode, _p(dy), _p(dw), _p(db), _p(ws), nbytes, B, cin, cout, hh, ww, 0)
+
+        def bn_backward(dz, x, residual, base, dx, c, hh, ww):
+            nbytes = int(lib.ppo_batchnorm_workspace_bytes(c))
+            ws = self._buf("bn_bwd_ws", ((nbytes + 7) // 8,), torch.float64)
+            self._call("ppo_batchnorm_running_backward_f32", _p(dz), _p(x), _p(residual), _p(self.params[base + ".weight"]),
+                       _p(self.buffers[base + ".running_mean"]), _p(self.buffers[base + ".running_var"]), _p(dx),
+                       _p(self.grads[base + ".weight"]), _p(self.grads[base + ".bias"]), _p(ws), nbytes, B, c, hh, ww,
+                       BN_EPS, 0)
+
+        for si in reversed(range(len(sp.stacks))):
+            cin, cout, hh, ww, ho, wo = sp.stacks[si]
+            fc = f"encoder.stacks.{si}.firstconv"
+            shape = (B, cout, ho, wo)
+            for bi in reversed(range(sp.n_block)):
+                base = f"encoder.stacks.{si}.blocks.{bi}"
+                q_in, z0, a, z1 = (acts[f"{k}{si}_{bi}{s}"] for k, s in (("q", "_in"), ("z0_", ""), ("a", ""), ("z1_", "")))
+                wgrad(z1, IN_RELU, g, base + ".conv1", cout, cout, ho, wo)
+                dz1 = self._buf(f"g{si}_{bi}_dz1", shape)
+                self._call(self._bwd_data_fn(base + ".conv1"), _p(g), _p(self._bwd_w(base + ".conv1")), _p(z1), None, _p(dz1),
+                           B, cout, cout, ho, wo)
+                da = self._buf(f"g{si}_{bi}_da", shape)
+                bn_backward(dz1, a, None, base + ".bn1", da, cout, ho, wo)
+                wgrad(z0, IN_RELU, da, base + ".conv0", cout, cout, ho, wo)
+                dz0 = self._buf(f"g{si}_{bi}_dz0", shape)
+                self._call(self._bwd_data_fn(base + ".conv0"), _p(da), _p(self._bwd_w(base + ".conv0")), _p(z0), None, _p(dz0),
+                           B, cout, cout, ho, wo)
+                gn = self._buf(f"g{si}_{bi}_in", shape)
+                bn_backward(dz0, q_in, g, base + ".bn0", gn, cout, ho, wo)
+                g = gn
+            x_in = acts[f"in{si}"]
+            mode = IN_NONE if si > 0 else (IN_U8 if x_in.dtype == torch.uint8 else IN_NONE)
+            g_prev = self._buf(f"g{si - 1}_top", (B, cin, hh, ww)) if si > 0 else None
+            if sp.down_sample == "stride":
+                nbytes = int(lib.ppo_conv3x3s2_any_wgrad_workspace_bytes(B, cin, cout, hh, ww))
+                ws = self._ws("wgrad_ws_" + fc, nbytes)
+                self._call("ppo_conv3x3s2_any_backward_weight_f32", _p(x_in), mode, _p(g), _p(self.grads[fc + ".weight"]),
+                           _p(self.grads[fc + ".bias"]), _p(ws), nbytes, B, cin, cout, hh, ww, 0)
+                if si > 0:
+                    self._call("ppo_conv3x3s2_any_backward_data_f32", _p(g), _p(self.params[fc + ".weight"]), None, None,
+                               _p(g_prev), B, cin, cout, hh, ww)
+            else:
+                dc = g
+                if sp.down_sample == "pool":
+                    dc = self._buf(f"g{si}_dc", (B, cout, hh, ww))
+                    self._call("ppo_maxpool3x3s2_backward_f32", _p(g), _p(acts[f"idx{si}"]), _p(dc), B, cout, hh, ww)
+                wgrad(x_in, mode, dc, fc, cin, cout, hh, ww)
+                if si > 0:
+                    self._call(self._bwd_data_fn(fc), _p(dc), _p(self._bwd_w(fc)), None, None, _p(g_prev), B, cin, cout, hh, ww)
+            g = g_prev
 
     def _backward_impala(self, acts, dh, dense_bias_done=False):
         """Backward through the encoder, every launch on the current stream: the dense layer, then stack by stack from
@@ -1769,7 +1967,8 @@ class DualHeadNet:
         gathered copy: uint8 images into the fused first convolution + max-pool, the pooled-gradient weight-gradient form.
         IMPALA only, and only where the first convolution has its specialised kernels (the generic ones take the gathered
         minibatch): the nature, rtg and mlp op-by-op paths take the gathered minibatch."""
-        if self.encoder_kind != "impala" or "encoder.stacks.0.firstconv" in self._generic or obs.dtype != torch.uint8 \
+        if self.encoder_kind != "impala" or self.batch_norm or "encoder.stacks.0.firstconv" in self._generic \
+                or obs.dtype != torch.uint8 \
                 or self.obs_norm is not None or not GATHER_IN_CONV or self.spec.down_sample != "pool":
             return False
         cin, cout, h, w, _ho, _wo = self.spec.stacks[0]
@@ -1984,7 +2183,7 @@ class DualHeadNet:
     def parameter_order(self):
         """Parameter names in the order of the reference module's `.parameters()` (= its state_dict order): the
         integer keys of torch.optim.Adam.state_dict()['state'] index this list."""
-        return list(self.state_dict().keys())
+        return [n for n in self.state_dict().keys() if n not in self.buffers]  # (buffers are no parameters)
 
     def adam_state_dict(self, exp_avg, exp_avg_sq, step, cfg=None):
         """The layout of `torch.optim.Adam(net.parameters()).state_dict()` — what the reference stores per optimiser
@@ -2103,6 +2302,19 @@ class TVFModel:
             # drawn after policy_net / value_net, as the reference's constructor does (rl/models.py:619-622)
             self.rnd = RNDNets(self.input_dims, self.obs_norm, self.device)
             self.prediction_net, self.target_net = self.rnd.prediction_net, self.rnd.target_net
+
+    def train(self, mode: bool = True):
+        """nn.Module.train for both nets (rl/rollout.py:712).  Only batch-norm nets read the flag (DualHeadNet.training)."""
+        self.policy_net.train(mode)
+        self.value_net.train(mode)
+        return self
+
+    def eval(self):
+        return self.train(False)
+
+    @property
+    def batch_norm(self) -> bool:
+        return self.policy_net.batch_norm
 
     def model_size(self, trainable_only: bool = True):
         n = self.policy_net.n_parameters()

@@ -130,6 +130,12 @@ class Runner:
                                       "of its own env columns and draw its own distil batch)")
         if args.sns.enabled and self.world > 1:
             raise NotImplementedError("noise-scale estimation under data parallelism is not built (a rank's gradients are not the batch's)")
+        # batch_norm=True in --model_encoder_args: the rollout's forwards normalise with their own batch's statistics
+        # (rl/rollout.py:712), so the env groups cannot run a step apart - see _rollout_pipelined
+        self.batch_norm = bool(getattr(model, "batch_norm", False))
+        if self.batch_norm and self.world > 1:
+            raise NotImplementedError("batch norm under data parallelism is not built (every rank would keep running "
+                                      "statistics of its own env columns)")
         # simple noise scale (rl/rollout.py:177): smoothed estimates per label, filled by ppo_amd/sns.py when --sns_enabled
         self.noise_stats = {}
         self._tvf_subset_weight_cache = {}
@@ -462,6 +468,14 @@ class Runner:
             # included); one launch on this group's stream writes its hashes, the tables follow after the rollout
             self.hash.hash_step(self.all_obs[t, lo:hi], t - 1, lo, hi)
 
+    def _policy_step_chunks(self, t, tag="i"):
+        """A batch-norm model's policy step at env step t: ONE step over all A envs on the current stream, in chunks of
+        --max_micro_batch_size in row order as detached_batch_forward cuts them (rl/rollout.py:558-598) - each chunk is
+        its own batch-norm batch and its own update of the running statistics, in both nets of a dual model."""
+        micro = max(int(args.max_micro_batch_size), 1)
+        for lo in range(0, self.A, micro):
+            self._policy_step(t, lo, min(self.A, lo + micro), tag=tag)
+
     def _hash_normed_row(self, t):
         """The normed hash inputs read the normaliser's constants as they stand after step t - 1's statistics update and
         before step t's (rl/rollout.py:735-741, 757): called between the upload of row t and norm.update(all_obs[t])."""
@@ -498,6 +512,13 @@ class Runner:
         other (the reference overlaps nothing: rl/rollout.py:792-816 is forward -> sync -> step)."""
         assert self.vec_env is not None, "Please attach vector environment first."
         N, A = self.N, self.A
+        self.model.train()  # rl/rollout.py:712 (read by batch-norm nets only); eval() again at the end, :927
+        try:
+            self._generate_rollout(N, A)
+        finally:
+            self.model.eval()
+
+    def _generate_rollout(self, N, A):
         self._finished_lengths = [[] for _ in range(N)]
         if self.intrinsic and self.rnd is None:
             self.int_rewards.zero_()  # rl/rollout.py:714 (with RND every element is written during the rollout)
@@ -612,6 +633,9 @@ class Runner:
             if s_ is not main:
                 s_.wait_stream(main)
         norm = self.model.obs_norm
+        # the groups run a step apart, each sending its own next observations up as it is stepped - unless a step needs
+        # every env's observations at once (observation normalisation, batch norm: the lock-step loop below)
+        own_upload = norm is None and not self.batch_norm
 
         # a group may be stepped (and uploaded) in several pieces: a leaf's H2D runs while the next leaf is stepped
         leaves = []
@@ -646,16 +670,16 @@ class Runner:
             # each leaf's next observations going up as soon as they exist
             events[i].synchronize()
             for leaf, lo, hi in leaves[i]:
-                if norm is None and UPLOAD_CHUNKS > 1 and hasattr(leaf, "step_upload"):
+                if own_upload and UPLOAD_CHUNKS > 1 and hasattr(leaf, "step_upload"):
                     # stepping and upload in one call: each quarter of the group goes up while the rest is stepped
                     torch.cuda.set_stream(copy_stream)
                     leaf.step_upload(act_np[lo:hi], rew_np[t, lo:hi], done_np[t, lo:hi], self.all_obs[t + 1, lo:hi],
                                      copy_stream, UPLOAD_CHUNKS)
                     continue
                 leaf.step_arrays(act_np[lo:hi], rew_np[t, lo:hi], done_np[t, lo:hi])
-                if norm is None:
+                if own_upload:
                     upload(i, t + 1, only=(leaf, lo, hi))
-            if norm is None:
+            if own_upload:
                 copy_events[i].record()  # (current stream = the copy stream: upload() left it so)
             lo, hi = bounds[i], bounds[i + 1]
             time_now, ep_len, ep_score = parts[i].last_episode_stats
@@ -665,12 +689,15 @@ class Runner:
 
         tags = [f"i{i}" if P > 1 else "i" for i in range(P)]
         host_rows = [self._actions_host[bounds[i]:bounds[i + 1]] for i in range(P)]
-        if norm is not None:
+        if norm is not None or self.batch_norm:
             # Observation normalisation: the running statistics take in EVERY env's observation of step t before any
             # group's forward of step t (rl/rollout.py:735-741), so the groups cannot run a step apart.  Per step: both
             # uploads, one statistics update on the first group's stream, then the groups' policy steps on their own
             # streams; the host steps group i while the GPU still runs the later groups' policy steps.  (The generic
             # path synchronised the whole device once per env step and overlapped nothing.)
+            # A batch-norm model has the same shape for another reason: a forward normalises with the statistics of its
+            # own batch, which is all A envs (in chunks, _policy_step_chunks), and every forward updates the running
+            # statistics, so the policy step is one, on the first group's stream, before any env is stepped.
             if not hasattr(self, "_norm_event"):
                 self._norm_event = torch.cuda.Event()
             try:
@@ -681,10 +708,17 @@ class Runner:
                     torch.cuda.set_stream(streams[0])
                     streams[0].wait_event(copy_events[0])
                     self._hash_normed_row(t)
-                    if t < N:
+                    if norm is not None and t < N:
                         norm.update(self.all_obs[t])
+                    if self.batch_norm:
+                        self._policy_step_chunks(t, tag=tags[0])
                     self._norm_event.record()
                     for i in range(P):
+                        if self.batch_norm:
+                            if t < N:  # (stream 0, behind the policy step)
+                                host_rows[i].copy_(self.actions[t, bounds[i]:bounds[i + 1]], non_blocking=True)
+                                events[i].record()
+                            continue
                         torch.cuda.set_stream(streams[i])
                         streams[i].wait_event(self._norm_event)
                         self._policy_step(t, bounds[i], bounds[i + 1], tag=tags[i], split_nets=split_nets)
@@ -744,7 +778,10 @@ class Runner:
             self._hash_normed_row(t)
             if norm is not None and t < N:
                 norm.update(self.all_obs[t])
-            self._policy_step(t)
+            if self.batch_norm:
+                self._policy_step_chunks(t)
+            else:
+                self._policy_step(t)
             if t == N:
                 break  # final state: only its value estimate is needed (rl/rollout.py:871-878)
             self._actions_host.copy_(self.actions[t], non_blocking=True)
@@ -772,6 +809,7 @@ class Runner:
         """Advantages (lambda_policy) and value targets (lambda_value) in one fused scan
         (rl/rollout.py:1182-1285 -> rl/returns.py:7-67), then the TVF return targets (rl/tvf.py:210-271)."""
         N, A = self.N, self.A
+        self.model.eval()  # rl/rollout.py:1192
         if self.replay_buffer is not None:
             # first, so that the draws of the add come before those of the TVF return sampler below and of the log lines
             # at the end, as in the reference (whose add closes generate_rollout, rl/rollout.py:956-969)
@@ -1319,6 +1357,7 @@ class Runner:
     def train(self):
         """rl/rollout.py:2220-2255: [distil] -> policy -> (dual) value -> [distil] -> [rnd]."""
         self._phase_stats = {}
+        self.model.eval()  # rl/rollout.py:2228
         if self.wants_distil_update("before_policy"):
             self.train_distil()
         self.train_policy()
