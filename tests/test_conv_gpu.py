@@ -3,6 +3,10 @@
 The reference runs these contractions through torch.nn.Conv2d (rl/impala.py:61-62,96);
 summation order differs between any two implementations, so the bar is the fp32
 tolerance SURVEY.md §8d gives for conv results: rel 1e-4 of the tensor's max.
+
+That bar is a smoke check.  The accuracy bar of these entry points is tests/test_conv_float64_gpu.py: float64
+references, a bound per element, an aggregate bar a reduced-precision path cannot meet, integer-exact runs at batches
+that wrap the persistent item loops, and the scalar epilogue of the wide geometries.
 """
 import numpy as np
 import pytest
