@@ -142,10 +142,17 @@ class StateHashTracker:
     # ------------------------------------------------------------------ after the rollout
     threshold = staticmethod(bonus_threshold)
 
-    def update_counts(self):
-        """rl/rollout.py:758-762 for the N steps of the rollout, in the reference's order, from obs_hashes."""
-        _call(self.lib, "ppo_hash_counts_update_f64", _p(self.obs_hashes), self.N, self.A, self.decay, _p(self.global_counts),
-              _p(self.recent_counts), self.n_bins)
+    def update_counts(self, hashes: torch.Tensor = None):
+        """rl/rollout.py:758-762 for the N steps of the rollout, in the reference's order, from obs_hashes - or from
+        `hashes`, a contiguous int32 [N, A'] tensor: under data parallelism the hashes of every rank's envs, so that the
+        tables count what all of them visited and stand identical on every rank (the bonus still reads obs_hashes)."""
+        if hashes is None:
+            hashes = self.obs_hashes
+        elif hashes.dtype != torch.int32 or hashes.dim() != 2 or hashes.shape[0] != self.N or not hashes.is_contiguous() \
+                or hashes.device != self.device:
+            raise ValueError(f"hashes must be a contiguous int32 [{self.N}, A] tensor on {self.device}")
+        _call(self.lib, "ppo_hash_counts_update_f64", _p(hashes), self.N, int(hashes.shape[1]), self.decay,
+              _p(self.global_counts), _p(self.recent_counts), self.n_bins)
 
     def add_bonus(self, int_rewards: torch.Tensor):
         """int_rewards[t, a] += bonus * g(recent[obs_hashes[t, a]]) with the final recent counts (rl/rollout.py:918-924)."""

@@ -11,6 +11,9 @@ The PPO path shards by env column, so the exchanges are:
     follow at the end and are latency-bound on xGMI.  The division by world size is folded into the Adam
     kernel (`grad_div`), the global-norm clip happens after the reduction so every rank clips alike;
   * `allreduce_sum_(moments)` once per batch — the three float64 advantage moments {sum, sumsq, n};
+  * with intrinsic rewards (`--rnd_enabled`, `--hash_enabled`): the RND predictor's flat gradient once per RND
+    optimiser step, in one bucket; `gather_columns` of the rollout's hashes (int32 [N, world*A]) once per rollout, of its
+    intrinsic rewards (and, without `--ir_propagation`, terminals) once per batch; the three `--ir_center` moments;
   * once at start-up, `broadcast_` of every replica's parameters (and optimiser / normaliser state) from
     rank 0, so replicas are identical whatever their process-local RNG drew.
 """
@@ -42,6 +45,28 @@ def broadcast_(t: torch.Tensor, src: int = 0) -> torch.Tensor:
     if world_size() > 1:
         dist.broadcast(t, src=src)
     return t
+
+
+def gather_columns(t: torch.Tensor) -> torch.Tensor:
+    """The global [N, world*A] array from each rank's [N, A] shard (float32, int32, uint8 or bool; device or host):
+    rank r's columns go to [r*A, (r+1)*A), the block `shard` gives it and the global env index the envs are seeded by.
+
+    Built from the one collective the tree relies on: every rank writes its block into a zeroed global buffer, then
+    `allreduce_sum_`.  x + 0 = x for every finite float and every integer, so the result carries the shards' bits (the one
+    thing lost is the sign of -0.0).  bool travels as uint8.  The collective is queued behind the writes on the current
+    stream and the current stream waits for it (nccl and gloo alike), so a later `.cpu()` reads the finished array.
+    With one rank the input itself is returned and nothing is issued."""
+    w = world_size()
+    if w == 1:
+        return t
+    if t.dim() != 2 or t.dtype not in (torch.float32, torch.int32, torch.uint8, torch.bool):
+        raise ValueError(f"gather_columns takes a float32 / int32 / uint8 / bool [N, A] tensor, not {t.dtype} {tuple(t.shape)}")
+    src = t.view(torch.uint8) if t.dtype == torch.bool else t
+    n, a = src.shape
+    out = torch.zeros((n, w * a), dtype=src.dtype, device=src.device)
+    out[:, rank() * a:(rank() + 1) * a].copy_(src)
+    allreduce_sum_(out)
+    return out.view(torch.bool) if t.dtype == torch.bool else out
 
 
 def assert_identical_across_ranks(tensors, what: str) -> str:

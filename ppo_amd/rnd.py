@@ -252,9 +252,10 @@ class RNDNets:
     def adam_step(self, lr=2.5e-4, beta1=0.9, beta2=0.999, eps=1e-5, max_grad_norm=20.0, grad_div=1.0,
                   grad_norm_out: Optional[torch.Tensor] = None, state=None):
         """Runner.optimizer_step(rnd_optimizer) (rl/rollout.py:1287-1321): clip_grad_norm_ + torch.optim.Adam.step over the
-        predictor's flat buffer."""
-        if state is not None or grad_div != 1.0:
-            raise NotImplementedError("the RND predictor has one set of Adam moments and trains on one GPU")
+        predictor's flat buffer.  `grad_div`: the data-parallel world size - the gradient arrives summed over ranks and the
+        kernel divides it before the clip, as for the other nets."""
+        if state is not None:
+            raise NotImplementedError("the RND predictor has one set of Adam moments")
         self._presummed = 0
         net = self.prediction_net
         if self.exp_avg is None:
@@ -263,7 +264,7 @@ class RNDNets:
         nbytes = int(self.lib.ppo_adam_workspace_bytes())
         ws = self._buf("adam_ws", ((nbytes + 3) // 4,))
         self._call("ppo_adam_step_f32", _p(net.flat), _p(net.grad), _p(self.exp_avg), _p(self.exp_avg_sq), net.flat.numel(),
-                   self.adam_steps, float(lr), float(beta1), float(beta2), float(eps), float(max_grad_norm), 1.0, _p(ws),
+                   self.adam_steps, float(lr), float(beta1), float(beta2), float(eps), float(max_grad_norm), float(grad_div), _p(ws),
                    _p(grad_norm_out))
 
     # ------------------------------------------------------------------ optimiser state (checkpoints)

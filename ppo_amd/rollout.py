@@ -31,7 +31,10 @@ What changed relative to the reference, and why (MI355X-first):
     go where is the reference's index arithmetic on its np.random draws (ppo_amd/replay.py `plan_add`);
   * data parallelism: env columns are sharded over ranks (one process per GPU); the only exchanges are one
     RCCL all-reduce of the flat gradient per optimiser step and one of the three advantage moments per
-    batch, so an N-GPU run equals a 1-GPU run with N*A envs up to minibatch composition.
+    batch, so an N-GPU run equals a 1-GPU run with N*A envs up to minibatch composition.  With intrinsic rewards on,
+    the three places that need the whole batch join them: the hash tables count every rank's hashes (one column gather
+    per rollout), the intrinsic-return filter runs on every rank over every rank's rewards (one or two gathers), and
+    `--ir_center` all-reduces its three moments; the RND predictor's gradient is reduced like the other nets'.
 """
 import copy
 import math
@@ -121,10 +124,6 @@ class Runner:
         if self.VH != (2 if self.intrinsic else 1):
             raise NotImplementedError("value heads: ('ext',), or ('ext', 'int') with intrinsic rewards (RND, the hash bonus)")
         self.world, self.rank = parallel.world_size(), parallel.rank()
-        if self.rnd is not None and self.world > 1:
-            raise NotImplementedError("RND under data parallelism is not built (the predictor's gradient is not reduced)")
-        if args.hash.enabled and self.world > 1:
-            raise NotImplementedError("state hashing under data parallelism is not built (per-rank count tables are not reduced)")
         if args.replay.enabled and self.world > 1:
             raise NotImplementedError("experience replay under data parallelism is not built (every rank would keep a buffer "
                                       "of its own env columns and draw its own distil batch)")
@@ -191,7 +190,8 @@ class Runner:
             self._rnd_stats = torch.zeros(_lib.PPO_RND_STATS, dtype=torch.float32, device=dev)
             self.intrinsic_reward_norm_scale = 1
             self.intrinsic_returns_rms = RunningMeanStd(shape=())
-            self.ems_norm = np.zeros([A])
+            # one entry per env of the whole run: the filter below runs on every rank over all ranks' rewards
+            self.ems_norm = np.zeros([A * self.world])
         # ---- state hashing (rl/rollout.py:253-274): the hashes of a rollout and the two count tables, all in HBM
         self.hash = None
         if args.hash.enabled:
@@ -249,6 +249,28 @@ class Runner:
                 red = parallel.GradReducer(net.grad, net.early_grad_offset)
                 self._reducers[id(net)] = red
                 net.grad_ready_hook = red.early
+            if self.rnd is not None:
+                # the predictor's gradient (split 0: no early bucket, the whole buffer is reduced in finish()), under the
+                # key optimizer_step looks its optimiser's net up by
+                self._reducers[id(self.rnd)] = parallel.GradReducer(self.rnd.grad, 0)
+                self._check_rnd_steps_agree()
+
+    def _rnd_steps(self):
+        """(rows, per-rank minibatch, optimiser steps) of one RND phase on this rank (train_rnd)."""
+        rows = round(self.N * self.A * args.rnd.experience_proportion)
+        mb = parallel.local_minibatch(args.rnd_opt.mini_batch_size)
+        return rows, mb, args.rnd_opt.epochs * (rows // max(mb, 1))
+
+    def _check_rnd_steps_agree(self):
+        """Every optimiser step of the predictor is a collective, so every rank must take the same number of them: said
+        here, once, when the ranks are known to be in step - a rank that took fewer would leave the others waiting in
+        an all-reduce."""
+        mine = self._rnd_steps()
+        got = [None] * self.world
+        torch.distributed.all_gather_object(got, mine)
+        if len(set(got)) != 1:
+            raise ValueError(f"the ranks would take different numbers of RND optimiser steps (rows, minibatch, steps per "
+                             f"rank: {got}); --agents, --n_steps and the --rnd_* flags must agree on every rank")
 
     def sync_replicas(self):
         """Data-parallel ranks must hold the same model: the only per-step exchange is the gradient all-reduce, so
@@ -264,6 +286,19 @@ class Runner:
                     tensors.append(t)
         if self.distil_optimizer is not None and self.distil_optimizer.state.exp_avg is not None:
             tensors += [self.distil_optimizer.state.exp_avg, self.distil_optimizer.state.exp_avg_sq]
+        rnd = self.rnd
+        if rnd is not None:
+            # the target is never trained, so replicas that drew their own would disagree for good; the predictor as the
+            # other nets.  Whether the moments exist is rank 0's to say: a rank without them allocates them to receive
+            has = torch.tensor([float(rnd.exp_avg is not None)], dtype=torch.float64, device=self.device)
+            parallel.broadcast_(has)
+            if has.item() and rnd.exp_avg is None:
+                rnd.exp_avg, rnd.exp_avg_sq = torch.zeros_like(rnd.prediction_net.flat), torch.zeros_like(rnd.prediction_net.flat)
+            elif not has.item():
+                rnd.exp_avg = rnd.exp_avg_sq = None
+            tensors += [rnd.target_net.flat, rnd.prediction_net.flat]
+            if rnd.exp_avg is not None:
+                tensors += [rnd.exp_avg, rnd.exp_avg_sq]
         norm = self.model.obs_norm
         if norm is not None:
             tensors += [norm.mean, norm.var, norm.mu, norm.std]
@@ -271,11 +306,13 @@ class Runner:
             parallel.broadcast_(t)
         for net in nets:
             net.mark_weights_changed()
-        counters = torch.tensor([float(n._adam_step) for n in nets] + [float(norm.count) if norm is not None else 0.0],
-                                dtype=torch.float64, device=self.device)
+        counters = torch.tensor([float(n._adam_step) for n in nets] + [float(rnd.adam_steps) if rnd is not None else 0.0]
+                                + [float(norm.count) if norm is not None else 0.0], dtype=torch.float64, device=self.device)
         parallel.broadcast_(counters)
         for n, c in zip(nets, counters[:len(nets)].tolist()):
             n._adam_step = int(c)
+        if rnd is not None:
+            rnd.adam_steps = int(counters[-2])
         if norm is not None:
             norm.count = float(counters[-1])
         return parallel.assert_identical_across_ranks(tensors, "model replicas")
@@ -485,8 +522,12 @@ class Runner:
     def _finish_hashing(self):
         """End of a rollout (rl/rollout.py:895-924): bring the tables up to date from obs_hashes, step by step in the
         reference's order - the env groups run a step apart, so it cannot happen during the rollout - then pay the bonus
-        from the final recent counts, before the clip of the intrinsic rewards (calculate_intrinsic_returns)."""
-        self.hash.update_counts()
+        from the final recent counts, before the clip of the intrinsic rewards (calculate_intrinsic_returns).
+
+        Data parallel: the tables count the hashes of every rank's envs (one gather, [N, world * A] int32), so they are
+        replicated - the tables a one-rank run over the same envs holds - and the bonus, the `binary` threshold and the
+        log lines read them as they are; the bonus goes to the rank's own columns."""
+        self.hash.update_counts(parallel.gather_columns(self.hash.obs_hashes) if self.world > 1 else None)
         if self.hash.bonus != 0:
             self.hash.add_bonus(self.int_rewards)
         if not args.disable_logging:
@@ -882,7 +923,16 @@ class Runner:
         records and ppo_scale_shift_clip_f32 follows."""
         N, A = self.N, self.A
         n = N * A
-        if args.ir.normalize:
+        if args.ir.normalize and self.world > 1:
+            # the filter runs on every rank over every rank's rewards [N, world * A] (and terminals), so ems_norm, the
+            # running variance and the scale are the one-rank run's and the same everywhere.  `.cpu()` is a copy on the
+            # current stream, which the gather has made wait for its collective: the host reads the finished array
+            rewards = np.clip(parallel.gather_columns(self.int_rewards).cpu().numpy(), -5, 5)  # :929
+            terminals = np.zeros(rewards.shape, bool) if args.ir.propagation \
+                else parallel.gather_columns(self.terminals).cpu().numpy()
+            self.ems_norm, self.intrinsic_reward_norm_scale = intrinsic_return_scale(
+                self.ems_norm, self.intrinsic_returns_rms, rewards, terminals, args.gamma_int, args.ir.propagation)
+        elif args.ir.normalize:
             self._int_rewards_host.copy_(self.int_rewards)
             rewards = np.clip(self._int_rewards_host.numpy(), -5, 5)  # :929
             terminals = self.terminals.cpu().numpy() if not args.ir.propagation else np.zeros((N, A), bool)
@@ -892,7 +942,9 @@ class Runner:
                    float(self.intrinsic_reward_norm_scale) if args.ir.normalize else 1.0, None, _p(self.int_rewards))
         if args.ir.center:
             # the mean of the scaled rewards, summed in float64 in a fixed order, then one more pass that subtracts it
+            # (the mean of the whole batch: the moments are summed over ranks first, as in _normalize_advantages)
             self._call("ppo_moments_f64", _p(self.int_rewards), n, _p(self._moments), _p(self._moments_ws))
+            parallel.allreduce_sum_(self._moments)
             self._call("ppo_scale_shift_clip_f32", _p(self.int_rewards), n, 0.0, 1.0, _p(self._moments), _p(self.int_rewards))
         self._head_value.copy_(self.int_value)
         value = self._head_value
@@ -915,6 +967,7 @@ class Runner:
         self._call("ppo_axpy_f32", _p(self.advantage), _p(int_advantage), float(args.ir.scale), n)
         if logging:
             self._call("ppo_moments_f64", _p(int_advantage), n, _p(self._adv_moments[1]), _p(self._moments_ws))
+            parallel.allreduce_sum_(self._adv_moments)  # the log lines speak of the whole batch
             (_e1, e2, _n), (i1, i2, cnt) = self._adv_moments.cpu().tolist()
             scale = float(args.ir.scale)
             mean = scale * i1 / cnt
@@ -1342,11 +1395,17 @@ class Runner:
 
     def train_rnd(self):
         """The predictor's phase (rl/rollout.py:1824-1841): --rnd_opt_epochs epochs of minibatches over the first
-        round(B * --rnd_experience_proportion) samples of the time-major batch, read through the minibatch index."""
+        round(B * --rnd_experience_proportion) samples of the time-major batch, read through the minibatch index.
+
+        Data parallel: B is the rank's share of the batch and the flag the GLOBAL minibatch, so the ranks take the steps
+        of a one-rank run together, each a collective (optimizer_step); that they all take the same number was checked
+        when the reducer was set up (_check_rnd_steps_agree), and that the rows divide into whole minibatches is
+        checked before the first of them (_run_epochs).  Feature statistics and loss_rnd are the rank's own, as the other
+        phases' statistics are."""
         if args.rnd_opt.epochs == 0:
             return
-        rows = round(self.N * self.A * args.rnd.experience_proportion)
-        if parallel.local_minibatch(args.rnd_opt.mini_batch_size) < 2:
+        rows, mb, _steps = self._rnd_steps()
+        if mb < 2:
             raise ValueError("--rnd_opt_mini_batch_size must be at least 2 (the feature variance over one row is NaN)")
         self._rnd_stats.zero_()
 
@@ -1615,6 +1674,9 @@ class Runner:
             self.model.obs_norm.load_state_dict(cp["obs_rms"])  # rl/rollout.py:511-513
         if self.intrinsic:  # rl/rollout.py:507-509
             self.ems_norm = np.asarray(cp["ems_norm"], np.float64).copy()
+            if self.ems_norm.shape != (self.A * self.world,):  # global state: one entry per env of the whole run
+                raise ValueError(f"ems_norm: {self.ems_norm.size} envs in the checkpoint, "
+                                 f"{self.A * self.world} in this run ({self.world} rank(s) of {self.A})")
             rms = cp["intrinsic_returns_rms"]
             self.intrinsic_returns_rms.restore_state((np.float64(rms["mean"]), np.float64(rms["var"]), rms["count"]))
         if args.sns.enabled:  # rl/rollout.py:495
