@@ -493,6 +493,37 @@ int ppo_ppo_loss_f32(const float *heads, int B, int ldo, int n_actions, int n_va
  * returns at row index[b] of the whole-batch arrays (the minibatch permutation), so those need no gather. */
 
 /*
+ * The same with SIDE, state-independent exploration (--side_*, rl/config.py:479-492; rl/rollout.py:1662-1679, target drawn
+ * at :1903-1918): the entropy bonus is replaced by a KL penalty towards a target policy, side_target_logp [n_actions] =
+ * its log-probabilities (one row for every sample).  With lp = log_softmax(logits), p = exp(lp), H = -sum p lp:
+ *   kl_penalty_b = sum_a p_a (lp_a - t_a) - H_b = -2 H_b - sum_a p_a t_a
+ *   gain_b       = min(rho*A, clip(rho)*A) - ent_coef * kl_penalty_b - sum_heads vf_coef*(V-R)^2
+ *   d(-gain_b)/dlogit_j = -[ w (1{j=act} - p_j) + ent_coef ( -2 p_j (lp_j + H) + p_j (t_j - sum_a p_a t_a) ) ]
+ * side_penalty (nullable, [B]) receives kl_penalty_b (row b of the minibatch, not index[b]).  The statistics row keeps
+ * its layout; its gain column holds the SIDE gain.  side_target_logp == NULL: ppo_ppo_loss_f32, bit for bit (the same
+ * launch), side_penalty untouched.
+ */
+int ppo_ppo_loss_side_f32(const float *heads, int B, int ldo, int n_actions, int n_value_heads, const int32_t *actions,
+                          const float *old_log_pac, const float *old_log_policy, const float *advantages,
+                          const float *returns, float eps_clip, float ent_coef, float vf_coef, float grad_scale,
+                          float *dheads, float *stats, const int32_t *index, const float *side_target_logp,
+                          float *side_penalty, void *stream);
+
+/*
+ * Global KL (--gkl_*, rl/config.py:378-394; rl/rollout.py:1723-1738, the states drawn at :1922-1934): KL(pi_new || pi_old)
+ * of the rows of a fixed sample of states, heads [B,ldo] = the training forward over them, old_log_policy [B,n_actions] =
+ * the log-policy recorded before the first update:
+ *   kl_b = sum_a p_a (lp_a - old_a)            kl_rows[b] = kl_b  (nullable)
+ *   dheads[b, a] = grad_scale * p_a ((lp_a - old_a) - kl_b),  dheads[b, n_actions..ldo) = 0
+ * The reference forms F.kl_div(..., reduction="batchmean") on the arrays flattened to [S * n_actions], so its global_kl is
+ * sum_b kl_b / (S * n_actions) over the S states of the sample; the penalty adds loss_scale * penalty * global_kl to the
+ * minibatch loss, i.e. grad_scale = penalty * loss_scale / (S * n_actions).
+ * PPO_E_INVALID before any launch: n_actions outside [1, 32], ldo < n_actions, a null heads / old_log_policy / dheads.
+ */
+int ppo_policy_kl_loss_f32(const float *heads, int B, int ldo, int n_actions, const float *old_log_policy,
+                           float grad_scale, float *dheads, float *kl_rows, void *stream);
+
+/*
  * Elementwise tanh and its backward dx = dy * (1 - y^2), y = tanh(x)  (torch.tanh at rl/models.py:166,
  * 456-457: the MLP encoder and the `tanh` encoder activation of the mujoco configs).
  */
@@ -960,7 +991,8 @@ typedef struct ppo_mlp_grads {
     float *dlog_std;                          /* [n_log_std] or NULL */
     int n_log_std;
 } ppo_mlp_grads;
-enum { PPO_MLP_LOSS_VALUE = 1, PPO_MLP_LOSS_DISTIL = 2, PPO_MLP_LOSS_GAUSSIAN = 3, PPO_MLP_LOSS_PPO = 4 };
+enum { PPO_MLP_LOSS_VALUE = 1, PPO_MLP_LOSS_DISTIL = 2, PPO_MLP_LOSS_GAUSSIAN = 3, PPO_MLP_LOSS_PPO = 4,
+       PPO_MLP_LOSS_POLICY_KL = 5 };
 typedef struct ppo_mlp_loss {
     int kind;         /* PPO_MLP_LOSS_* : the arguments of ppo_value_loss_f32 / ppo_distil_loss_f32 / ppo_gaussian_loss_f32 /
                          ppo_ppo_loss_f32, same meaning */
@@ -989,6 +1021,11 @@ typedef struct ppo_mlp_loss {
     float distil_delta, distil_l1_scale;
     const int32_t *pred_actions;
     int n_active;
+    /* PPO_MLP_LOSS_PPO: the added arguments of ppo_ppo_loss_side_f32 (zero = ppo_ppo_loss_f32).
+     * PPO_MLP_LOSS_POLICY_KL: the arguments of ppo_policy_kl_loss_f32 - n_actions, old_log_policy ([B, n_actions], read at
+     * minibatch row b: `index` applies to x alone), grad_scale, stats = kl_rows [B]; one statistics column (n_stats = 1). */
+    const float *side_target_logp;
+    float *side_penalty;
 } ppo_mlp_loss;
 int ppo_mlp_supported(int F, int H, int NH);
 int ppo_mlp_forward_f32(const float *x, const ppo_mlp_net *net, const int32_t *index, int B, float *heads, float *h_pre,

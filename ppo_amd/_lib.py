@@ -73,6 +73,8 @@ SIGNATURES = {
     "ppo_synth_env_get_state": (_i, [_vp, _vp, _vp, _vp]),
     "ppo_synth_env_set_state": (_i, [_vp, _vp, _vp, _vp, _vp]),
     "ppo_ppo_loss_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _vp, _vp, _vp, _vp]),
+    "ppo_ppo_loss_side_f32": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _f, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ppo_policy_kl_loss_f32": (_i, [_vp, _i, _i, _i, _vp, _f, _vp, _vp, _vp]),
     "ppo_conv3x3_pool_forward_f32": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "ppo_conv3x3_packed_floats": (_sz, [_i, _i, _i]),
     "ppo_conv3x3_pack_weights_f32": (_i, [_vp, _i, _vp]),
@@ -228,10 +230,11 @@ class MlpLoss(ctypes.Structure):
                 ("ent_coef", ctypes.c_float), ("dlog_std_rows", ctypes.c_void_p),
                 ("distil_policy_loss", ctypes.c_int), ("distil_value_loss", ctypes.c_int),
                 ("distil_delta", ctypes.c_float), ("distil_l1_scale", ctypes.c_float),
-                ("pred_actions", ctypes.c_void_p), ("n_active", ctypes.c_int)]
+                ("pred_actions", ctypes.c_void_p), ("n_active", ctypes.c_int),
+                ("side_target_logp", ctypes.c_void_p), ("side_penalty", ctypes.c_void_p)]
 
 
-MLP_LOSS_VALUE, MLP_LOSS_DISTIL, MLP_LOSS_GAUSSIAN, MLP_LOSS_PPO = 1, 2, 3, 4
+MLP_LOSS_VALUE, MLP_LOSS_DISTIL, MLP_LOSS_GAUSSIAN, MLP_LOSS_PPO, MLP_LOSS_POLICY_KL = 1, 2, 3, 4, 5
 # PPO_DISTIL_POLICY_* / PPO_DISTIL_VALUE_* (include/ppo_amd.h), by the reference's flag values
 DISTIL_POLICY_LOSSES = {"kl_policy": 0, "mse_policy": 1, "mse_logit": 2}
 DISTIL_VALUE_LOSSES = {"mse": 0, "l1": 1, "clipped_mse": 2, "huber": 3}

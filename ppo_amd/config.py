@@ -6,8 +6,9 @@ singleton read at call time; grouped flags appear as `--<prefix>_<name>` and are
 Flags of out-of-scope subsystems are accepted and ignored with a
 note, so existing launch lines keep working.  The `hash` group is registered only on a launch line that enables hashing
 (`--hash_enabled[=True]`), the `replay` group only on one that names a `--replay_mode` other than `off`, the `sns` group
-only on one that enables noise-scale estimation (`--sns_enabled[=True]`): every other line parses exactly as it did before
-state hashing, the replay buffer and the simple noise scale were built.
+only on one that enables noise-scale estimation (`--sns_enabled[=True]`), the `gkl` and `side` groups only on one that
+enables them (`--gkl_enabled[=True]`, `--side_enabled[=True]`): every other line parses exactly as it did before state
+hashing, the replay buffer, the simple noise scale, the global KL penalty and state-independent exploration were built.
 """
 import argparse
 import sys
@@ -295,6 +296,36 @@ def replay_mode_on(argv):
     return False
 
 
+class GlobalKLConfig(_Group):  # rl/config.py:378-394
+    FIELDS = (
+        ("enabled", bool, False, "estimate KL(new || old) over a fixed random sample of the rollout's states"),
+        ("threshold", float, -1, "read nowhere (as in the reference)"),
+        ("penalty", float, 0.01, "penalty on the global KL in the policy loss, 0 = the statistic only"),
+        ("source", str, "rollout", "[rollout]"),
+        ("samples", int, 1024, "number of states in the global sample"),
+    )
+
+
+class SIDEConfig(_Group):  # rl/config.py:479-492
+    FIELDS = (
+        ("enabled", bool, False, "state-independent exploration: a KL penalty towards a random target policy"),
+        ("noise_std", float, 0.1, "standard deviation of the target policy's logits"),
+        ("period", int, 10, "redraw the target every n rollouts"),
+    )
+
+
+def gkl_enabled_on(argv):
+    """Whether a launch line enables the global KL penalty (`--gkl_enabled[=True]`): only then are the `gkl` flags
+    registered."""
+    return _flag_enabled_on(argv, "--gkl_enabled")
+
+
+def side_enabled_on(argv):
+    """Whether a launch line enables state-independent exploration (`--side_enabled[=True]`): only then are the `side`
+    flags registered."""
+    return _flag_enabled_on(argv, "--side_enabled")
+
+
 class IRConfig(_Group):  # rl/config.py:445-455
     FIELDS = (
         ("propagation", bool, True, "intrinsic returns propagate through the end of an episode"),
@@ -319,6 +350,8 @@ class Config:
         self.hash = HashConfig("hash")  # not in _groups: registered per launch line (setup)
         self.replay = ReplayConfig("replay")  # likewise
         self.sns = SimpleNoiseScaleConfig("sns")  # likewise
+        self.gkl = GlobalKLConfig("gkl")  # likewise
+        self.side = SIDEConfig("side")  # likewise
         # (a flag belongs to the group with the longest matching prefix: rnd_opt_lr is rnd_opt's, rnd_enabled is rnd's)
         self._groups = (self.policy_opt, self.value_opt, self.distil_opt, self.distil, self.model, self.env, self.tvf,
                         self.rnd_opt, self.rnd, self.ir)
@@ -465,8 +498,11 @@ class Config:
         self.hash = HashConfig("hash")
         self.replay = ReplayConfig("replay")  # the same for the replay flags and a --replay_mode other than off
         self.sns = SimpleNoiseScaleConfig("sns")  # and for the sns flags and --sns_enabled
+        self.gkl = GlobalKLConfig("gkl")  # and for the gkl flags and --gkl_enabled
+        self.side = SIDEConfig("side")  # and for the side flags and --side_enabled
         optional = ((self.hash,) if hashing_enabled_on(argv) else ()) + ((self.replay,) if replay_mode_on(argv) else ()) \
-            + ((self.sns,) if sns_enabled_on(argv) else ())
+            + ((self.sns,) if sns_enabled_on(argv) else ()) + ((self.gkl,) if gkl_enabled_on(argv) else ()) \
+            + ((self.side,) if side_enabled_on(argv) else ())
         groups = self._groups + optional
         for g in optional:
             g.add(parser)
@@ -540,6 +576,13 @@ class Config:
                                  f"{self.batch_size}, which is the policy estimate's b_big")
             if set(labels) - {"policy"} and self.sns.b_big % self.sns.b_small:
                 raise ValueError(f"--sns_b_small={self.sns.b_small} must divide --sns_b_big={self.sns.b_big}")
+        if self.gkl.enabled:
+            if self.gkl.source != "rollout":  # asserted in the middle of an update by the reference (rl/rollout.py:1924)
+                raise ValueError(f"--gkl_source={self.gkl.source}: only rollout source supported at the moment")
+            if self.gkl.samples < 1:
+                raise ValueError(f"--gkl_samples={self.gkl.samples} must be at least 1")
+        if self.side.enabled and self.side.period < 1:
+            raise ValueError(f"--side_period={self.side.period} must be at least 1")
         # EnvConfig.auto (rl/config.py:563-600)
         if self.env.frame_skip in (None, -1):
             self.env.frame_skip = 4 if self.env.type == "atari" else 1
@@ -571,7 +614,8 @@ class Config:
         d = {k: v for k, v in vars(self).items() if not k.startswith("_") and not isinstance(v, _Group)}
         d["use_intrinsic_rewards"] = self.use_intrinsic_rewards
         for g in self._groups + ((self.hash,) if self.hash.enabled else ()) + ((self.replay,) if self.replay.enabled else ()) \
-                + ((self.sns,) if self.sns.enabled else ()):
+                + ((self.sns,) if self.sns.enabled else ()) + ((self.gkl,) if self.gkl.enabled else ()) \
+                + ((self.side,) if self.side.enabled else ()):
             d.update(g.flatten())
         return d
 

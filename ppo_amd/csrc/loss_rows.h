@@ -290,11 +290,17 @@ struct PpoLossP {
     const float *old_log_pac, *old_log_policy, *advantages, *returns;
     float eps_clip, ent_coef, vf_coef, grad_scale;
     float *stats;
+    // SIDE (rl/rollout.py:1662-1679), read by the SIDE instantiations only: the target policy's log-probabilities [nA] and
+    // (nullable) the [B] array that receives each sample's kl_penalty
+    const float *side_target_logp;
+    float *side_penalty;
 };
 // one THREAD per sample (`store` true), or - in the dense + heads + loss launch, where the head row sits in a wave's lanes
 // and z(i) is a shuffle - every lane of the wave on the same values with one lane storing.  NA: the action count at
-// compile time (0 = any).  z(i): head output i of the sample.
-template <int NA, class Z>
+// compile time (0 = any).  z(i): head output i of the sample.  SIDE: the entropy bonus is replaced by the KL penalty towards
+// q.side_target_logp, kl_penalty = sum_a p_a (lp_a - t_a) - H = -2 H - sum_a p_a t_a, gain = loss_clip - ent_coef * kl_penalty
+// - vloss; a template flag, so the instantiations without it are the code they were.
+template <int NA, bool SIDE = false, class Z>
 __device__ __forceinline__ void ppo_loss_row_z(const PpoLossP &q, Z z, float *dz, int b, int sb, bool store)
 {
     const int nA = NA ? NA : q.nA;
@@ -328,6 +334,12 @@ __device__ __forceinline__ void ppo_loss_row_z(const PpoLossP &q, Z z, float *dz
         if (old_log_policy) kl_true += p * (lp[a] - oldp[a]);
         logpac = a == act ? lp[a] : logpac;
     }
+    float side_pt = 0.f;  // sum_a p_a t_a
+    if constexpr (SIDE) {
+#pragma unroll kUnroll
+        for (int a = 0; a < nA; ++a) side_pt += expf(lp[a]) * q.side_target_logp[a];
+    }
+    const float side_kl = -2.f * entropy - side_pt;
     const float ratio = expf(logpac - old_log_pac[sb]);
     const float clipped_ratio = fminf(fmaxf(ratio, 1.f - eps_clip), 1.f + eps_clip);
     const float s1 = ratio * adv, s2 = clipped_ratio * adv;
@@ -355,7 +367,9 @@ __device__ __forceinline__ void ppo_loss_row_z(const PpoLossP &q, Z z, float *dz
     for (int a = 0; a < nA; ++a) {
         const float p = expf(lp[a]);
         const float dpg = w * ((a == act ? 1.f : 0.f) - p);
-        const float dent = -p * (lp[a] + entropy);
+        float dent = -p * (lp[a] + entropy);
+        // d(-kl_penalty)/dlogit_j = 2 dH/dlogit_j + p_j (t_j - sum_a p_a t_a)
+        if constexpr (SIDE) dent = 2.f * dent + p * (q.side_target_logp[a] - side_pt);
         if (store) dz[a] = -grad_scale * (dpg + ent_coef * dent);
     }
     if (stats && store) {
@@ -366,15 +380,58 @@ __device__ __forceinline__ void ppo_loss_row_z(const PpoLossP &q, Z z, float *dz
         s[ST_CLIPPED] = fabsf(ratio - 1.f) > eps_clip ? 1.f : 0.f;
         s[ST_KL_APPROX] = old_log_pac[sb] - logpac;
         s[ST_KL_TRUE] = kl_true;
-        s[ST_GAIN] = loss_clip + ent_coef * entropy - vloss;
+        s[ST_GAIN] = SIDE ? loss_clip - ent_coef * side_kl - vloss : loss_clip + ent_coef * entropy - vloss;
         s[ST_RATIO] = ratio;
     }
+    if constexpr (SIDE)
+        if (q.side_penalty && store) q.side_penalty[b] = side_kl;
 }
 
-template <int NA>
+template <int NA, bool SIDE = false>
 __device__ __forceinline__ void ppo_loss_row(const PpoLossP &q, const float *z, float *dz, int b, int sb)
 {
-    ppo_loss_row_z<NA>(q, [&](int i) { return z[i]; }, dz, b, sb, true);
+    ppo_loss_row_z<NA, SIDE>(q, [&](int i) { return z[i]; }, dz, b, sb, true);
+}
+
+// ---------------------------------------------------------------------------------------------- global KL (policy phase)
+// KL(pi_new || pi_old) of one state of the global sample (rl/rollout.py:1723-1738), one THREAD per sample as the PPO row:
+// kl_b = sum_a p_a (lp_a - old_a), d kl_b / d z_j = p_j ((lp_j - old_j) - kl_b) (the arithmetic of distil_loss_row's
+// DP_KL_POLICY term).  No value column takes part and there are no target arrays: columns [nA, ldo) get zero.
+struct PolicyKlP {
+    int ldo, nA;
+    const float *old_log_policy;  // [B, nA], row b
+    float grad_scale;
+    float *kl_rows;               // [B] nullable
+};
+template <int NA>
+__device__ __forceinline__ void policy_kl_row(const PolicyKlP &q, const float *z, float *dz, int b)
+{
+    const int nA = NA ? NA : q.nA;
+    constexpr int kUnroll = NA ? 32 : 1;
+    const float *old = q.old_log_policy + (size_t)b * nA;
+    float lp[NA ? NA : kMaxActions], d[NA ? NA : kMaxActions];
+    float mx = -INFINITY;
+#pragma unroll kUnroll
+    for (int a = 0; a < nA; ++a) {
+        lp[a] = z[a];
+        d[a] = old[a];
+        mx = fmaxf(mx, lp[a]);
+    }
+    float se = 0.f;
+#pragma unroll kUnroll
+    for (int a = 0; a < nA; ++a) se += expf(lp[a] - mx);
+    const float lse = mx + logf(se);
+    float kl = 0.f;
+#pragma unroll kUnroll
+    for (int a = 0; a < nA; ++a) {
+        lp[a] -= lse;
+        d[a] = lp[a] - d[a];
+        kl += expf(lp[a]) * d[a];
+    }
+#pragma unroll kUnroll
+    for (int a = 0; a < nA; ++a) dz[a] = q.grad_scale * expf(lp[a]) * (d[a] - kl);
+    for (int i = nA; i < q.ldo; ++i) dz[i] = 0.f;
+    if (q.kl_rows) q.kl_rows[b] = kl;
 }
 
 }  // namespace ppo

@@ -40,7 +40,7 @@ constexpr int kRows = 16;        // rows of a tile
 constexpr int kMlpWaves = 16;
 constexpr int kMlpThreads = kMlpWaves * 64;
 
-enum { MLP_LOSS_NONE = 0, MLP_LOSS_VALUE, MLP_LOSS_DISTIL, MLP_LOSS_GAUSS, MLP_LOSS_PPO };
+enum { MLP_LOSS_NONE = 0, MLP_LOSS_VALUE, MLP_LOSS_DISTIL, MLP_LOSS_GAUSS, MLP_LOSS_PPO, MLP_LOSS_PPO_SIDE, MLP_LOSS_POLICY_KL };
 enum { ACT_NONE = 0, ACT_TANH, ACT_RELU };
 
 struct MlpArgs {
@@ -59,6 +59,7 @@ struct MlpArgs {
     DistilLossP ld;
     GaussLossP lg;
     PpoLossP lp;
+    PolicyKlP lk;
     int ldx, ldh, ldo;       // LDS row strides (floats), each = 4 (mod 32)
     int lds_floats;          // floats of LDS the tiles take; 64 per wave follow (the sink of the cache-warming requests)
 };
@@ -361,7 +362,11 @@ __global__ __launch_bounds__(kMlpThreads) void mlp_rows_kernel(const MlpArgs a)
         else if (a.loss == MLP_LOSS_DISTIL) distil_loss_row(a.ld, z, dz, b, sb, lane);
         else if (a.loss == MLP_LOSS_GAUSS)
             gaussian_loss_row(a.lg, z, dz, a.dlog_std_rows ? a.dlog_std_rows + (size_t)b * a.lg.nA : nullptr, b, sb, lane);
-        else if (lane == 0) ppo_loss_row<0>(a.lp, z, dz, b, sb);
+        else if (a.loss == MLP_LOSS_PPO_SIDE) {
+            if (lane == 0) ppo_loss_row<0, true>(a.lp, z, dz, b, sb);
+        } else if (a.loss == MLP_LOSS_POLICY_KL) {
+            if (lane == 0) policy_kl_row<0>(a.lk, z, dz, b);  // old_log_policy is read at minibatch row b, not through the index
+        } else if (lane == 0) ppo_loss_row<0>(a.lp, z, dz, b, sb);
     }
     lds_barrier();
     if (PPO_TUNE_MLP_STOP == 5) return;
@@ -649,9 +654,18 @@ extern "C" int ppo_mlp_train_f32(const float *x, const ppo_mlp_net *net, const p
                 NH < loss->n_actions + loss->n_value_heads || !loss->actions_i || !loss->old_log_pac || !loss->advantages ||
                 (loss->n_value_heads > 0 && !loss->returns))
                 return fail(PPO_E_INVALID, "ppo_mlp_train_f32: bad ppo-loss arguments");
-            a.loss = MLP_LOSS_PPO;
+            a.loss = loss->side_target_logp ? MLP_LOSS_PPO_SIDE : MLP_LOSS_PPO;
             a.lp = PpoLossP{NH, loss->n_actions, loss->n_value_heads, loss->actions_i, loss->old_log_pac, loss->old_log_policy,
-                            loss->advantages, loss->returns, loss->eps_clip, loss->ent_coef, loss->vf_coef, loss->grad_scale, loss->stats};
+                            loss->advantages, loss->returns, loss->eps_clip, loss->ent_coef, loss->vf_coef, loss->grad_scale, loss->stats,
+                            loss->side_target_logp, loss->side_target_logp ? loss->side_penalty : nullptr};
+            break;
+        case PPO_MLP_LOSS_POLICY_KL:
+            if (loss->n_actions <= 0 || loss->n_actions > kMaxActions || NH < loss->n_actions || !loss->old_log_policy)
+                return fail(PPO_E_INVALID, "ppo_mlp_train_f32: bad policy-kl arguments");
+            if (stat_sums && n_stats != 1)
+                return fail(PPO_E_INVALID, "ppo_mlp_train_f32: the policy-kl loss has one statistics column (n_stats %d)", n_stats);
+            a.loss = MLP_LOSS_POLICY_KL;
+            a.lk = PolicyKlP{NH, loss->n_actions, loss->old_log_policy, loss->grad_scale, loss->stats};
             break;
         default:
             return fail(PPO_E_INVALID, "ppo_mlp_train_f32: unknown loss kind %d", loss->kind);

@@ -10,6 +10,9 @@
 //                         Runner.train_policy_minibatch (rl/rollout.py:1640-1660,1682,1744-1753,
 //                         1596-1608), forward AND the gradient w.r.t. the head outputs, plus the
 //                         per-sample statistics the reference logs.
+//  * ppo_ppo_loss_side_f32   the same with SIDE, state-independent exploration (rl/rollout.py:1662-1679): the entropy
+//                         bonus becomes a KL penalty towards a random target policy.
+//  * ppo_policy_kl_loss_f32  KL(new || old) over the global sample of states (rl/rollout.py:1723-1738) and its gradient.
 //
 // Head outputs arrive as one row per sample: [ policy logits (n_actions) | value heads (vh) | ... ],
 // leading dimension ldo; columns past n_actions + vh get zero gradient (the reference's
@@ -42,6 +45,24 @@ __global__ __launch_bounds__(64) void ppo_loss_kernel(const float *__restrict__ 
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
     ppo_loss_row<NA>(p, heads + (size_t)b * p.ldo, dheads + (size_t)b * p.ldo, b, index ? index[b] : b);
+}
+
+template <int NA>
+__global__ __launch_bounds__(64) void ppo_loss_side_kernel(const float *__restrict__ heads, int B, PpoLossP p,
+                                                           float *__restrict__ dheads, const int32_t *__restrict__ index)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    ppo_loss_row<NA, true>(p, heads + (size_t)b * p.ldo, dheads + (size_t)b * p.ldo, b, index ? index[b] : b);
+}
+
+template <int NA>
+__global__ __launch_bounds__(64) void policy_kl_kernel(const float *__restrict__ heads, int B, PolicyKlP p,
+                                                       float *__restrict__ dheads)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    policy_kl_row<NA>(p, heads + (size_t)b * p.ldo, dheads + (size_t)b * p.ldo, b);
 }
 
 }  // namespace
@@ -107,4 +128,67 @@ extern "C" int ppo_ppo_loss_f32(const float *heads, int B, int ldo, int n_action
     }
 #undef PPO_LOSS_CASE
     return check_launch("ppo_loss_kernel");
+}
+
+extern "C" int ppo_ppo_loss_side_f32(const float *heads, int B, int ldo, int n_actions, int n_value_heads,
+                                     const int32_t *actions, const float *old_log_pac, const float *old_log_policy,
+                                     const float *advantages, const float *returns, float eps_clip, float ent_coef,
+                                     float vf_coef, float grad_scale, float *dheads, float *stats, const int32_t *index,
+                                     const float *side_target_logp, float *side_penalty, void *stream)
+{
+    using namespace ppo;
+    // no target: the launch ppo_ppo_loss_f32 makes, its instantiations untouched
+    if (!side_target_logp)
+        return ppo_ppo_loss_f32(heads, B, ldo, n_actions, n_value_heads, actions, old_log_pac, old_log_policy, advantages,
+                                returns, eps_clip, ent_coef, vf_coef, grad_scale, dheads, stats, index, stream);
+    if (B < 0 || n_actions <= 0 || n_actions > kMaxActions || n_value_heads < 0 || ldo < n_actions + n_value_heads)
+        return fail(PPO_E_INVALID, "ppo_ppo_loss_side_f32: bad shape");
+    if (B == 0) return PPO_OK;
+    if (!heads || !actions || !old_log_pac || !advantages || !dheads || (n_value_heads > 0 && !returns))
+        return fail(PPO_E_INVALID, "ppo_ppo_loss_side_f32: null pointer");
+    const PpoLossP p{ldo, n_actions, n_value_heads, actions, old_log_pac, old_log_policy, advantages, returns, eps_clip,
+                     ent_coef, vf_coef, grad_scale, stats, side_target_logp, side_penalty};
+#define PPO_LOSS_CASE(NA)                                                                                               \
+    case NA:                                                                                                            \
+        hipLaunchKernelGGL((ppo_loss_side_kernel<NA>), dim3((B + 63) / 64), dim3(64), 0, as_stream(stream), heads, B, p, \
+                           dheads, index);                                                                              \
+        break;
+    switch (n_actions) {
+        PPO_LOSS_CASE(4)
+        PPO_LOSS_CASE(6)
+        PPO_LOSS_CASE(15)
+        PPO_LOSS_CASE(18)
+        default:
+            hipLaunchKernelGGL((ppo_loss_side_kernel<0>), dim3((B + 63) / 64), dim3(64), 0, as_stream(stream), heads, B, p,
+                               dheads, index);
+    }
+#undef PPO_LOSS_CASE
+    return check_launch("ppo_loss_side_kernel");
+}
+
+extern "C" int ppo_policy_kl_loss_f32(const float *heads, int B, int ldo, int n_actions, const float *old_log_policy,
+                                      float grad_scale, float *dheads, float *kl_rows, void *stream)
+{
+    using namespace ppo;
+    if (B < 0 || n_actions <= 0 || n_actions > kMaxActions || ldo < n_actions)
+        return fail(PPO_E_INVALID, "ppo_policy_kl_loss_f32: bad shape (B=%d n_actions=%d ldo=%d, max %d actions)", B, n_actions,
+                    ldo, kMaxActions);
+    if (B == 0) return PPO_OK;
+    if (!heads || !old_log_policy || !dheads) return fail(PPO_E_INVALID, "ppo_policy_kl_loss_f32: null pointer");
+    const PolicyKlP p{ldo, n_actions, old_log_policy, grad_scale, kl_rows};
+#define PPO_KL_CASE(NA)                                                                                                \
+    case NA:                                                                                                           \
+        hipLaunchKernelGGL((policy_kl_kernel<NA>), dim3((B + 63) / 64), dim3(64), 0, as_stream(stream), heads, B, p,    \
+                           dheads);                                                                                    \
+        break;
+    switch (n_actions) {
+        PPO_KL_CASE(4)
+        PPO_KL_CASE(6)
+        PPO_KL_CASE(15)
+        PPO_KL_CASE(18)
+        default:
+            hipLaunchKernelGGL((policy_kl_kernel<0>), dim3((B + 63) / 64), dim3(64), 0, as_stream(stream), heads, B, p, dheads);
+    }
+#undef PPO_KL_CASE
+    return check_launch("policy_kl_kernel");
 }

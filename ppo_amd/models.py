@@ -2000,7 +2000,7 @@ class DualHeadNet:
 
     def ppo_minibatch(self, prev_state, actions, old_log_pac, old_log_policy, advantages, returns,
                       eps_clip=0.2, ent_coef=0.01, vf_coef=0.5, loss_scale=1.0, index=None, stat_sums=None,
-                      stat_accumulate=False, obs_indexed=False):
+                      stat_accumulate=False, obs_indexed=False, side_target_logp=None, side_penalty=None):
         """Forward, fused PPO loss, backward: gradients of mean(-gain)*loss_scale land in self.grad
         (Runner.train_policy_minibatch, rl/rollout.py:1610-1771; discrete actions).  vf_coef = 0 (and
         returns None) leaves the value head out, as the dual architecture's policy phase does (:1744).
@@ -2012,7 +2012,14 @@ class DualHeadNet:
         prev_state.shape[0] is (B included).  Needs ``index``, and a net that can read through it (takes_obs_index,
         or the fused MLP path without observation normalisation); anything else raises ValueError.
         Returns the per-sample statistics tensor [B, 8] (device).  MLP nets on the fused path (mlp_fused) also take
-        ``stat_sums``, a device row that receives the column sums of the statistics."""
+        ``stat_sums``, a device row that receives the column sums of the statistics.
+        ``side_target_logp`` ([n_actions] float32 log-probabilities): SIDE (rl/rollout.py:1662-1679) - the entropy bonus
+        becomes -ent_coef * (KL(new || target) - H); ``side_penalty`` ([B] float32, optional) receives that penalty per
+        sample.  The loss then runs as a launch of its own (ppo_ppo_loss_side_f32), not on the dense + heads launch."""
+        if side_target_logp is not None:
+            self._check_policy_rows("side_target_logp", side_target_logp, None)
+        elif side_penalty is not None:
+            raise ValueError("side_penalty without side_target_logp")
         if self.mlp_fused:
             B = self._minibatch_rows(prev_state, index, obs_indexed)
             return self._mlp_train(
@@ -2020,7 +2027,8 @@ class DualHeadNet:
                 obs_indexed=obs_indexed, grad_scale=float(loss_scale) / B, n_actions=self.n_actions,
                 n_value_heads=self.vh if returns is not None else 0,
                 returns=_p(returns), vf_coef=float(vf_coef), actions_i=_p(actions), old_log_pac=_p(old_log_pac),
-                old_log_policy=_p(old_log_policy), advantages=_p(advantages), eps_clip=float(eps_clip), ent_coef=float(ent_coef))
+                old_log_policy=_p(old_log_policy), advantages=_p(advantages), eps_clip=float(eps_clip), ent_coef=float(ent_coef),
+                side_target_logp=_p(side_target_logp), side_penalty=_p(side_penalty))
         B = self._minibatch_rows(prev_state, index, obs_indexed)
         stats = self._buf("loss_stats", (B, 8))
         vh = self.vh if returns is not None else 0
@@ -2029,11 +2037,71 @@ class DualHeadNet:
                      _p(self._buf("dheads", (B, self.nh))), _p(stats), _p(index))
         # the loss rides on the dense + heads launch of the training forward where that launch exists (_dense_heads: image
         # encoders with relu; ppo_dense_heads_loss_forward_f32, bit-identical, one latency-bound launch less per minibatch)
+        if side_target_logp is not None:
+            acts, o, B, dheads = self._train_forward(prev_state, index, obs_indexed)
+            self._call("ppo_ppo_loss_side_f32", _p(o), B, self.nh, *loss_args, _p(side_target_logp), _p(side_penalty))
+            self.backward(acts, dheads)
+            return stats
         acts, o, B, dheads = self._train_forward(prev_state, index, obs_indexed, tail=loss_args)
         if not acts["tail_taken"]:
             self._call("ppo_ppo_loss_f32", _p(o), B, self.nh, *loss_args)
         self.backward(acts, dheads)
         return stats
+
+    def _check_policy_rows(self, name, t, rows):
+        """A [rows, n_actions] (rows None: [n_actions]) contiguous float32 device array of a discrete policy."""
+        if self.n_actions > 32:
+            raise ValueError(f"{name}: discrete policies only (at most 32 actions, this net has {self.n_actions})")
+        want = (self.n_actions,) if rows is None else (rows, self.n_actions)
+        if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != want:
+            raise ValueError(f"{name} must be a contiguous float32 {list(want)} tensor, got {t.dtype} {list(t.shape)}")
+
+    def policy_kl_minibatch(self, prev_state, old_log_policy, penalty_scale, loss_scale=1.0, index=None, obs_indexed=False,
+                            stat_sums=None, stat_accumulate=False):
+        """The global KL pass (rl/rollout.py:1723-1738): training forward over a chunk of the global states, KL(new || old)
+        per state against old_log_policy [B, n_actions] (row b belongs to state b of the chunk: ``index`` applies to
+        prev_state alone), backward: the gradient of penalty_scale * loss_scale * sum_b kl_b lands in self.grad.  The
+        caller folds the reference's divisor in: penalty_scale = penalty / (S * n_actions) for a sample of S states.
+        prev_state, ``index`` and ``obs_indexed`` as in ppo_minibatch.  Returns kl_b [B, 1] (device); MLP nets on the
+        fused path also take ``stat_sums``, a one-element device row that receives (or is added) their sum."""
+        B = self._minibatch_rows(prev_state, index, obs_indexed)
+        self._check_policy_rows("old_log_policy", old_log_policy, B)
+        scale = float(penalty_scale) * float(loss_scale)
+        kl = self._buf("kl_rows", (B, 1))
+        if self.mlp_fused:
+            return self._mlp_train(_lib.MLP_LOSS_POLICY_KL, prev_state, index, kl, 1, stat_sums, stat_accumulate,
+                                   obs_indexed=obs_indexed, grad_scale=scale, n_actions=self.n_actions,
+                                   old_log_policy=_p(old_log_policy))
+        acts, o, B, dheads = self._train_forward(prev_state, index, obs_indexed)
+        self._call("ppo_policy_kl_loss_f32", _p(o), B, self.nh, self.n_actions, _p(old_log_policy), scale, _p(dheads), _p(kl))
+        self.backward(acts, dheads)
+        return kl
+
+    def policy_kl_rows(self, prev_state, old_log_policy, index=None, obs_indexed=False):
+        """kl_b [B, 1] of policy_kl_minibatch without its backward pass (--gkl_penalty=0: the statistic alone); self.grad
+        and the optimiser's sums of g^2 stay as they are."""
+        B = self._minibatch_rows(prev_state, index, obs_indexed)
+        self._check_policy_rows("old_log_policy", old_log_policy, B)
+        kl = self._buf("kl_rows", (B, 1))
+        if self.mlp_fused:
+            x = prev_state
+            if x.dtype != torch.float32 or not x.is_contiguous():
+                raise ValueError("the mlp encoder takes contiguous float32 observations")
+            if self.obs_norm is not None:  # as _mlp_train
+                if obs_indexed:
+                    raise ValueError("observation normalisation needs the gathered minibatch")
+                xn = self._buf("txn", tuple(x.shape))
+                self._call("ppo_obs_normalize_f32", _p(x), 0, _p(self.obs_norm.mu), _p(self.obs_norm.std),
+                           self.obs_norm.norm_eps, _p(xn), x.shape[0], self.obs_norm.F)
+                x = xn
+            o = self._buf("klheads", (B, self.nh))
+            self._call("ppo_mlp_forward_f32", _p(x), ctypes.addressof(self._mlp_net), _p(index) if obs_indexed else None,
+                       B, _p(o), None, None)
+        else:
+            _acts, o, B, _dheads = self._train_forward(prev_state, index, obs_indexed)
+        self._call("ppo_policy_kl_loss_f32", _p(o), B, self.nh, self.n_actions, _p(old_log_policy), 0.0,
+                   _p(self._buf("kl_dheads", (B, self.nh))), _p(kl))
+        return kl
 
     def gaussian_minibatch(self, prev_state, actions, old_log_pac, advantages, returns, eps_clip=0.2, vf_coef=0.5,
                            loss_scale=1.0, index=None, stat_sums=None, stat_accumulate=False, obs_indexed=False):

@@ -135,6 +135,28 @@ class Runner:
         if self.batch_norm and self.world > 1:
             raise NotImplementedError("batch norm under data parallelism is not built (every rank would keep running "
                                       "statistics of its own env columns)")
+        # ---- the policy phase's regularisers: global KL (rl/rollout.py:1723-1738) and SIDE (:1662-1679)
+        if args.gkl.enabled or args.side.enabled:
+            if action_dist != "discrete":
+                raise ValueError("--gkl_enabled / --side_enabled: discrete policies only (the reference's global KL reads "
+                                 "log_policy, which a gaussian policy lacks; its SIDE refuses mujoco)")
+            if args.side.enabled and args.env.type == "mujoco":
+                raise ValueError("--side_enabled: not supported for mujoco (rl/rollout.py:1907)")
+        if args.gkl.enabled:
+            if self.world > 1:
+                raise NotImplementedError("the global KL penalty under data parallelism is not built (every rank would draw "
+                                          "its global states from its own env columns: the estimate, and the gradient of "
+                                          "its penalty, need one sample and one sum across the ranks)")
+            if args.gkl.samples > args.n_steps * args.agents:
+                raise ValueError(f"--gkl_samples={args.gkl.samples} exceeds the rollout, n_steps x agents = "
+                                 f"{args.n_steps * args.agents} (the states are drawn without replacement)")
+            if args.gkl.samples % min(args.max_micro_batch_size, args.gkl.samples):
+                raise ValueError(f"--gkl_samples={args.gkl.samples} is not a multiple of --max_micro_batch_size="
+                                 f"{args.max_micro_batch_size}, the chunk of the global pass")
+        self.side_target_policy_logp = None  # [n_actions] device; not saved in checkpoints, as in the reference
+        self._mb_pos = None  # (minibatch, micro-batch) of the step function _run_epochs is calling
+        self._policy_extra = None  # the policy phase's global-KL / SIDE statistics rows (train_policy, fetch_stats)
+        self._gkl_rows = None  # the rollout rows of the global states of the last policy phase ([S] int32, device)
         # simple noise scale (rl/rollout.py:177): smoothed estimates per label, filled by ppo_amd/sns.py when --sns_enabled
         self.noise_stats = {}
         self._tvf_subset_weight_cache = {}
@@ -1108,7 +1130,51 @@ class Runner:
                 step_fn(mb_obs, idx, 1.0)
         return one_pass
 
-    def _run_epochs(self, label, optimizer, epochs, mini_batch_size, step_fn, n_stats, rows=None, obs=None):
+    class _GlobalKLPass:
+        """The global KL pass of a policy minibatch (rl/rollout.py:1723-1738): KL(new || old) over the S global states
+        `rows` (rows of the rollout, [S] int32 device) against `old` [S, nA], in chunks of at most --max_micro_batch_size
+        states, through the input form the phase uses.  With a penalty every chunk is a forward + backward pass whose
+        gradient joins the minibatch's accumulator (n_passes of them); with --gkl_penalty=0 it is a forward alone.  The
+        reference repeats the pass in every micro-batch at scale 1 / micro_batches; here it runs once at scale 1."""
+
+        def __init__(self, runner, net, rows, old, stat_rows):
+            self.r, self.net, self.rows, self.old, self.stat_rows = runner, net, rows, old, stat_rows
+            self.S = int(rows.shape[0])
+            self.chunk = min(args.max_micro_batch_size, self.S)
+            self.penalty = float(args.gkl.penalty)
+            self.n_passes = self.S // self.chunk if self.penalty != 0 else 0
+
+        def run(self, k, after_backward, form, obs_all, obs_rows, row_bytes, B):
+            net, r, nA = self.net, self.r, self.r.n_actions
+            scale = self.penalty / (self.S * nA)  # F.kl_div's "batchmean" over the arrays flattened to [S * nA]
+            for c, lo in enumerate(range(0, self.S, self.chunk)):
+                idx, old = self.rows[lo:lo + self.chunk], self.old[lo:lo + self.chunk]
+                out = self.stat_rows[k]
+                if self.penalty == 0:
+                    if form == "gather":
+                        x = net._buf("gkl_obs", (self.chunk, *r.state_shape), r.all_obs.dtype)
+                        r._call("ppo_gather_rows", _p(obs_rows), row_bytes, B, _p(idx), self.chunk, _p(x))
+                        kl = net.policy_kl_rows(x, old)
+                    else:
+                        kl = net.policy_kl_rows(obs_rows if form == "fused" else obs_all, old, index=idx, obs_indexed=True)
+                    r._call("ppo_colsum_f32", _p(kl), self.chunk, 1, 1, _p(out), 1 if c else 0)
+                    continue
+                if form == "fused":
+                    net.policy_kl_minibatch(obs_rows, old, scale, index=idx, obs_indexed=True, stat_sums=out,
+                                            stat_accumulate=bool(c))
+                    after_backward()
+                    continue
+                if form == "in_conv":
+                    kl = net.policy_kl_minibatch(obs_all, old, scale, index=idx, obs_indexed=True)
+                else:
+                    x = net._buf("gkl_obs", (self.chunk, *r.state_shape), r.all_obs.dtype)
+                    r._call("ppo_gather_rows", _p(obs_rows), row_bytes, B, _p(idx), self.chunk, _p(x))
+                    kl = net.policy_kl_minibatch(x, old, scale)
+                after_backward()
+                r._call("ppo_colsum_f32", _p(kl), self.chunk, 1, 1, _p(out), 1 if c else 0)
+
+    def _run_epochs(self, label, optimizer, epochs, mini_batch_size, step_fn, n_stats, rows=None, obs=None,
+                    extra_pass=None, stat_rows=None):
         """Permutation minibatching over the rollout (rl/rollout.py:2257-2407): per epoch one host shuffle
         (np.random, as the reference :2319-2320); per minibatch — in micro-batches of at most --max_micro_batch_size
         samples, gradients accumulated, each pass scaled by 1 / micro_batches (:2331-2374) — gather the observations,
@@ -1116,7 +1182,10 @@ class Runner:
         are column-summed into one device row per minibatch.  `rows`: train on the first `rows` samples of the
         time-major batch only (the RND phase, rl/rollout.py:1830).  `obs`: a contiguous device tensor [S, *state_shape]
         of the rollout's dtype to train over instead of the rollout's observations (the distil batch drawn from the replay
-        buffer); the per-sample data step_fn reads through the index then has S rows too."""
+        buffer); the per-sample data step_fn reads through the index then has S rows too.  `extra_pass`: passes that follow
+        a minibatch's micro-batches (_GlobalKLPass): extra_pass.n_passes of them write net.grad and join the accumulator,
+        so the optimiser sees the sum of all passes and the data-parallel early-bucket hook stays parked until it is
+        complete.  `stat_rows`: the [epochs * minibatches, n_stats] device rows to use instead of the label's own."""
         if obs is None:
             B = self.N * self.A if rows is None else int(rows)
             obs_all = self.all_obs[:self.N].view(self.N * self.A, *self.state_shape)[:B]
@@ -1140,7 +1209,12 @@ class Runner:
         # ... and the IMPALA nets read uint8 image rows through the permutation in their first convolution
         in_conv = not fused and hasattr(net, "takes_obs_index") and net.takes_obs_index(self.all_obs)
         mb_obs = None if (fused or in_conv) else net._buf("mb_obs", (micro, *self.state_shape), self.all_obs.dtype)
-        stat_rows = net._buf(f"stat_rows_{label}", (epochs * n_mb, n_stats))
+        if stat_rows is None:
+            stat_rows = net._buf(f"stat_rows_{label}", (epochs * n_mb, n_stats))
+        elif tuple(stat_rows.shape) != (epochs * n_mb, n_stats) or not stat_rows.is_contiguous():
+            raise ValueError(f"stat_rows must be a contiguous [{epochs * n_mb}, {n_stats}] tensor")
+        form = "fused" if fused else ("in_conv" if in_conv else "gather")
+        n_extra = extra_pass.n_passes if extra_pass is not None else 0
         norm_rows = net._buf(f"norm_rows_{label}", (epochs * n_mb,))
         if args.sns.enabled and epochs > 0 and sns.wants_noise_estimate(self, label):
             # noise of the first update only, before epoch 0's shuffle (rl/rollout.py:2290-2294)
@@ -1154,10 +1228,11 @@ class Runner:
             np.random.shuffle(ordering)
             order_dev = torch.from_numpy(ordering).to(self.device, non_blocking=True)
             for j in range(n_mb):
-                acc = self._Accumulator(self, net, n_micro)
+                acc = self._Accumulator(self, net, n_micro + n_extra)
                 try:
                     for u in range(n_micro):
                         idx = order_dev[j * mb + u * micro:j * mb + (u + 1) * micro]
+                        self._mb_pos = (k, u)  # for step functions that keep statistics rows of their own (SIDE)
                         if fused:
                             step_fn(obs_rows, idx, 1.0 / n_micro, stat_sums=stat_rows[k], stat_accumulate=bool(u),
                                     obs_indexed=True)
@@ -1170,9 +1245,12 @@ class Runner:
                             stats = step_fn(mb_obs, idx, 1.0 / n_micro)
                         acc.after_backward()
                         self._call("ppo_colsum_f32", _p(stats), micro, n_stats, n_stats, _p(stat_rows[k]), 1 if u else 0)
+                    if extra_pass is not None:
+                        extra_pass.run(k, acc.after_backward, form, obs_all, obs_rows, row_bytes, B)
                     acc.finish()
                 finally:
                     acc.restore_hook()
+                    self._mb_pos = None
                 self.optimizer_step(optimizer, label, norm_out=norm_rows[k:k + 1])  # the norm lands in its row: no copy launch
                 k += 1
         self._phase_stats[label] = (stat_rows, norm_rows, mb)
@@ -1187,11 +1265,58 @@ class Runner:
         self._normalize_advantages()
         returns = None if self.dual else self.returns
         net.zero_untouched_grads()
+        epochs = args.policy_opt.epochs
+        extra_pass = stat_rows = side_t = side_stat = None
+        self._policy_extra = None
+        if args.gkl.enabled or args.side.enabled:
+            # one buffer for the phase's statistics - the eight PPO columns, then the global KL sums, then the SIDE penalty
+            # sums, a row per minibatch each - so that fetch_stats reads them in one device->host copy
+            n = epochs * (B // parallel.local_minibatch(args.policy_opt.mini_batch_size))
+            flat = net._buf("stat_rows_policy_reg", (n * 10,))
+            flat.zero_()
+            stat_rows, gkl_stat, side_stat = flat[:8 * n].view(n, 8), flat[8 * n:9 * n].view(n, 1), flat[9 * n:].view(n, 1)
+            self._policy_extra = {"flat": flat, "n": n, "gkl": bool(args.gkl.enabled), "side": bool(args.side.enabled),
+                                  "S": int(args.gkl.samples)}
+        if args.side.enabled:
+            # the target policy of state-independent exploration (rl/rollout.py:1903-1918): redrawn every --side_period
+            # rollouts, the reference's draw on the model's device (under data parallelism rank 0's, for all)
+            if self.side_target_policy_logp is None or self.batch_counter % args.side.period == 0:
+                bias = torch.normal(0, args.side.noise_std, size=[self.n_actions], dtype=torch.float32, device=self.device)
+                if self.world > 1:
+                    parallel.broadcast_(bias)
+                self.side_target_policy_logp = torch.log_softmax(bias, dim=0).contiguous()
+                if not args.disable_logging:
+                    t = self.side_target_policy_logp.double()
+                    self.log.watch_mean("side_target_entropy", float(-(t.exp() * t).sum()), display_name="ste")
+            side_t = self.side_target_policy_logp
+        if args.gkl.enabled:
+            # the global states (rl/rollout.py:1922-1934): a draw without replacement from the rollout, at the reference's
+            # place in the np.random stream (before epoch 0's shuffle), and the policy on them before the first update
+            S = int(args.gkl.samples)
+            rows_host = np.random.choice(B, S, replace=False)
+            self._gkl_rows = torch.from_numpy(rows_host.astype(np.int32)).to(self.device)
+            old = net._buf("gkl_old_log_policy", (S, self.n_actions))
+            obs_rows = self.all_obs[:self.N].view(B, -1)
+            chunk = min(args.max_micro_batch_size, S)
+            x = net._buf("gkl_obs", (chunk, *self.state_shape), self.all_obs.dtype)
+            for lo in range(0, S, chunk):
+                self._call("ppo_gather_rows", _p(obs_rows), obs_rows.shape[1] * obs_rows.element_size(), B,
+                           _p(self._gkl_rows[lo:lo + chunk]), chunk, _p(x))
+                old[lo:lo + chunk].copy_(net.forward(x, exclude_value=True)["log_policy"])
+            extra_pass = self._GlobalKLPass(self, net, self._gkl_rows, old, gkl_stat)
         if self.action_dist == "discrete":
             def step(mb_obs, idx, loss_scale, **kw):
-                return net.ppo_minibatch(mb_obs, self.actions, self.log_pac, self.log_policy, self.norm_advantage,
-                                         returns, eps_clip=self.ppo_epsilon, ent_coef=self.current_entropy_bonus,
-                                         vf_coef=args.ppo_vf_coef, loss_scale=loss_scale, index=idx, **kw)
+                pen = None
+                if side_t is not None and self._mb_pos is not None:
+                    pen = net._buf("side_penalty", (int(idx.shape[0]), 1))
+                stats = net.ppo_minibatch(mb_obs, self.actions, self.log_pac, self.log_policy, self.norm_advantage,
+                                          returns, eps_clip=self.ppo_epsilon, ent_coef=self.current_entropy_bonus,
+                                          vf_coef=args.ppo_vf_coef, loss_scale=loss_scale, index=idx,
+                                          side_target_logp=side_t, side_penalty=pen, **kw)
+                if pen is not None:
+                    k, u = self._mb_pos
+                    self._call("ppo_colsum_f32", _p(pen), pen.shape[0], 1, 1, _p(side_stat[k]), 1 if u else 0)
+                return stats
         else:
             actions, log_pac = self.actions.view(B, self.n_actions), self.log_pac.view(B, self.n_actions)
 
@@ -1199,8 +1324,8 @@ class Runner:
                 return net.gaussian_minibatch(mb_obs, actions, log_pac, self.norm_advantage, returns,
                                               eps_clip=self.ppo_epsilon, vf_coef=args.ppo_vf_coef, loss_scale=loss_scale,
                                               index=idx, **kw)
-        self._run_epochs("policy", self.policy_optimizer, args.policy_opt.epochs, args.policy_opt.mini_batch_size,
-                         step, 8)
+        self._run_epochs("policy", self.policy_optimizer, epochs, args.policy_opt.mini_batch_size, step, 8,
+                         extra_pass=extra_pass, stat_rows=stat_rows)
 
     def train_value(self):
         """Value phase of the dual architecture (rl/rollout.py:1956-2004): value_net regresses the value
@@ -1431,19 +1556,56 @@ class Runner:
     # ---- the reference's dict-based minibatch API (rl/rollout.py:1331, 1513, 1610, 2257), for callers that
     # drive the phases themselves; `data` holds minibatch-sized device tensors
     def train_policy_minibatch(self, data, loss_scale=1.0):
+        """rl/rollout.py:1610-1771.  With --side_enabled the target is self.side_target_policy_logp; with --gkl_enabled
+        `data` also holds "*global_states" [S, *state_shape] and "*global_log_policy" [S, n_actions], and the result
+        "global_kl" (a host tensor, as the reference's)."""
         net = self.policy_net
         returns = data.get("returns") if not self.dual else None
+        side_pen = None
         if self.action_dist == "discrete":
+            side_t = None
+            if args.side.enabled:
+                side_t = self.side_target_policy_logp
+                if side_t is None:
+                    raise ValueError("--side_enabled: no target policy yet (train_policy draws side_target_policy_logp)")
+                side_pen = net._buf("side_penalty", (int(data["prev_state"].shape[0]), 1))
             stats = net.ppo_minibatch(data["prev_state"], data["actions"].to(torch.int32), data["log_pac"],
                                       data.get("log_policy"), data["advantages"], returns, eps_clip=self.ppo_epsilon,
                                       ent_coef=self.current_entropy_bonus, vf_coef=args.ppo_vf_coef,
-                                      loss_scale=loss_scale)
+                                      loss_scale=loss_scale, side_target_logp=side_t, side_penalty=side_pen)
         else:
             stats = net.gaussian_minibatch(data["prev_state"], data["actions"], data["log_pac"], data["advantages"],
                                            returns, eps_clip=self.ppo_epsilon, vf_coef=args.ppo_vf_coef,
                                            loss_scale=loss_scale)
         s = stats.double().mean(0).cpu().numpy()
-        return {"loss": float(-s[6] * loss_scale), "kl_approx": float(s[4]), "kl_true": float(s[5]), "clip_frac": float(s[3])}
+        result = {"loss": float(-s[6] * loss_scale), "kl_approx": float(s[4]), "kl_true": float(s[5]), "clip_frac": float(s[3])}
+        if side_pen is not None and not args.disable_logging:
+            t = self.side_target_policy_logp.double()
+            self.log.watch_mean("side_kl_penalty", float(side_pen.double().mean()), display_name="skl")
+            self.log.watch_mean("side_target_entropy", float(-(t.exp() * t).sum()), display_name="ste")
+        if args.gkl.enabled:
+            states = self.model.prep_for_model(data["*global_states"])
+            old = data["*global_log_policy"].to(self.device, torch.float32).contiguous()
+            S = int(states.shape[0])
+            div = S * self.n_actions  # F.kl_div's "batchmean" over the arrays flattened to [S * n_actions] (:1728-1731)
+            if args.gkl.penalty != 0:
+                # the second forward + backward of the minibatch: its gradient is added to the PPO pass's
+                ppo_grad = net._buf("grad_ppo_pass", tuple(net.grad.shape))
+                ppo_grad.copy_(net.grad)
+                kl = net.policy_kl_minibatch(states, old, args.gkl.penalty / div, loss_scale=loss_scale)
+                self._call("ppo_accumulate_f32", _p(net.grad), _p(ppo_grad), net.grad.numel())
+                net._presummed = 0  # the sums of g^2 the KL pass left are not the summed gradient's
+            else:
+                kl = net.policy_kl_rows(states, old)
+            global_kl = kl.double().sum().cpu() / div
+            if args.gkl.penalty != 0:
+                gkl_loss = float(global_kl) * args.gkl.penalty
+                result["loss"] += gkl_loss * loss_scale  # -gain, and gkl_loss comes off every sample's gain (:1735)
+                if not args.disable_logging:
+                    self.log.watch_mean("*loss_gkl", gkl_loss, history_length=64 * args.policy_opt.epochs,
+                                        display_name="ls_gkl", display_width=8)
+            result["global_kl"] = global_kl.to(torch.float32)
+        return result
 
     @staticmethod
     def _required_tvf_heads(single_value_head):
@@ -1572,11 +1734,27 @@ class Runner:
         out = {}
         if "policy" in self._phase_stats:
             stat_rows, norm_rows, mb = self._phase_stats["policy"]
-            s = stat_rows.cpu().numpy().astype(np.float64) / mb
+            extra = self._policy_extra
+            if extra is None:
+                s = stat_rows.cpu().numpy().astype(np.float64) / mb
+            else:  # the PPO columns, the global KL sums and the SIDE penalty sums in the one copy (train_policy)
+                n = extra["n"]
+                flat = extra["flat"].cpu().numpy().astype(np.float64)
+                s = flat[:8 * n].reshape(n, 8) / mb
             out.update({"loss_pg": s[:, 0].mean(), "entropy": s[:, 1].mean(), "loss_v_ext": s[:, 2].mean(),
                         "clip_frac": s[:, 3].mean(), "kl_approx": s[:, 4].mean(), "kl_true": s[:, 5].mean(),
                         "loss_policy": s[:, 6].mean(), "grad_policy": float(norm_rows.mean().item()),
                         "adv_mean": float(self._mean_std[0].item()), "adv_std": float(self._mean_std[1].item())})
+            if extra is not None and extra["gkl"]:
+                # global_kl per minibatch: the sum of the rows' KL over S * n_actions (F.kl_div's "batchmean" on the
+                # flattened arrays, rl/rollout.py:1728-1731); with a penalty, gkl_loss comes off every sample's gain (:1735)
+                global_kl = flat[8 * n:9 * n] / (extra["S"] * self.n_actions)
+                out["global_kl"] = global_kl.mean()
+                if args.gkl.penalty != 0:
+                    out["*loss_gkl"] = (args.gkl.penalty * global_kl).mean()
+                    out["loss_policy"] -= out["*loss_gkl"]
+            if extra is not None and extra["side"]:
+                out["side_kl_penalty"] = (flat[9 * n:] / mb).mean()
         if "value" in self._phase_stats:
             stat_rows, norm_rows, mb = self._phase_stats["value"]
             s = stat_rows.cpu().numpy().astype(np.float64) / mb
@@ -1595,8 +1773,10 @@ class Runner:
                         "*feat_mean": feat_mean / calls, "*feat_var": feat_var / calls, "*feat_max": feat_max,
                         "grad_rnd": float(norm_rows.mean().item())})
         if not args.disable_logging:
+            named = {"*loss_gkl": dict(history_length=64 * args.policy_opt.epochs, display_name="ls_gkl", display_width=8),
+                     "side_kl_penalty": dict(display_name="skl")}  # rl/rollout.py:1736, 1678
             for k_, v in out.items():
-                self.log.watch_mean(k_, v)
+                self.log.watch_mean(k_, v, **named.get(k_, {}))
         return out
 
     # ------------------------------------------------------------------ checkpoints (rl/rollout.py:394-517)
