@@ -401,6 +401,24 @@ int ppo_conv2d_strided_backward_weight_leaky_f32(const void *in, int in_mode, co
                                                  int stride, void *stream);
 
 /*
+ * OPT-IN reduced precision (`--precision=medium|low`, the reference's train.py:166-178, whose default `medium` lets
+ * cuDNN run these convolutions in TF32): the three ReLU launches above with every product as three bf16 MFMAs on
+ * (hi, lo) splits of both operands, float32 accumulation (csrc/conv_strided_bf16x3.hip, tile loop csrc/
+ * conv_gemm_tile_bf16x3.h).  Per element |result - exact| <= 2^-15 * sum |a| |b| plus the float32 summation error.
+ * Same arguments, validation, error codes, workspace (ppo_conv2d_strided_wgrad_workspace_bytes) and fixed summation
+ * order - every launch gives the same bits; the slab reduction stays float32.  Operands are split inside the launch:
+ * nothing is packed.  Non-finite inputs are outside the contract (an infinite operand gives NaN).
+ */
+int ppo_conv2d_strided_forward_bf16x3(const void *in, int in_mode, const float *weight, const float *bias, float *out,
+                                      int relu_out, int n, int cin, int h, int w, int cout, int kh, int kw, int stride,
+                                      void *stream);
+int ppo_conv2d_strided_backward_data_bf16x3(const float *dy, const float *gate, const float *weight, float *dx, int n,
+                                            int cin, int h, int w, int cout, int kh, int kw, int stride, void *stream);
+int ppo_conv2d_strided_backward_weight_bf16x3(const void *in, int in_mode, const float *dy, const float *gate,
+                                              float *dweight, float *dbias, void *workspace, size_t workspace_bytes, int n,
+                                              int cin, int h, int w, int cout, int kh, int kw, int stride, void *stream);
+
+/*
  * C[m,n] = epi( sum_k fa(A[m,k]) * fb(B[k,n]) + bias[n] ),  f32 MFMA.
  * A element (m,k) at A[m*a_sm + k*a_sk]; B element (k,n) at B[k*b_sk + n*b_sn]; C row-major with ldc.
  * relu_a / relu_b: apply max(.,0) to that operand on load.  bias [N], mask [M,ldc] nullable;

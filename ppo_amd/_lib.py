@@ -164,6 +164,10 @@ SIGNATURES = {
     "ppo_conv2d_strided_backward_data_leaky_f32": (_i, [_vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "ppo_conv2d_strided_backward_weight_leaky_f32": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _sz, _f, _i, _i, _i, _i, _i, _i, _i,
                                                           _i, _vp]),
+    "ppo_conv2d_strided_forward_bf16x3": (_i, [_vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "ppo_conv2d_strided_backward_data_bf16x3": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "ppo_conv2d_strided_backward_weight_bf16x3": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp, _sz, _i, _i, _i, _i, _i, _i, _i, _i,
+                                                       _vp]),
     "ppo_obs_normalize_channel_f32": (_i, [_vp, _i, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _i, _i, _vp]),
     "ppo_rnd_error_f32": (_i, [_vp, _vp, _i, _i, _vp, _i64, _vp, _f, _vp, _vp]),
     "ppo_scale_shift_clip_f32": (_i, [_vp, _i64, _f, _d, _vp, _vp, _vp]),

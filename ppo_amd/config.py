@@ -479,8 +479,9 @@ class Config:
         a("--threads", type=int, default=self.threads)
         a("--precision", type=str, default=self.precision,
           help="[low|medium|high] (train.py:166-178): high = exact float32 everywhere; low / medium also allow the "
-               "split-bf16 launches (3 bf16 MFMAs per product, ~16-bit products) where they exist - the residual blocks of "
-               "the IMPALA encoder's 32-channel stacks")
+               "split-bf16 launches (3 bf16 MFMAs per product, ~16-bit products) where they exist - the IMPALA encoder's "
+               "16- and 32-channel convolutions and the nature encoder's convolution passes listed in models.NATURE_SPLIT; "
+               "rtg, mlp, batch-norm nets and the RND networks stay exact float32")
         # accepted as before; the value follows --rnd_enabled, as the reference's property of that name (rl/config.py:881)
         a("--use_intrinsic_rewards", type=str2bool, nargs="?", const=True, default=False)
         a("--sync_envs", type=str2bool, nargs="?", const=True, default=False)

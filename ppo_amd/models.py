@@ -109,6 +109,16 @@ FUSE_MLP = int(os.environ.get("PPO_AMD_FUSE_MLP", "1"))
 # uint8 image minibatches are read out of the whole rollout batch through the permutation by the first convolution (and by
 # its weight gradient) instead of being gathered into a second buffer by a launch of its own (0 = gather first)
 GATHER_IN_CONV = int(os.environ.get("PPO_AMD_GATHER_IN_CONV", "1"))
+# --precision=medium|low with the nature encoder: the (layer, pass) pairs that run as split-bf16 launches (csrc/
+# conv_strided_bf16x3.hip) instead of the exact float32 ones.  A pair is listed only where tools/nature_split_ab.py
+# measured the split launch faster than the exact one by more than the block-to-block spread at n = 128 and n = 256
+# (the table: profiles/nature_kernels.md "Timing").
+# The weight gradients of conv2 and conv3 are not listed: split / exact 0.98 - 1.01, inside the spread.
+NATURE_SPLIT = frozenset({
+    ("conv1", "forward"), ("conv1", "backward_weight"),
+    ("conv2", "forward"), ("conv2", "backward_data"),
+    ("conv3", "forward"), ("conv3", "backward_data"),
+})
 HEAD_NAMES = ("policy_head", "value_head", "advantage_head", "tvf_head")
 BN_EPS, BN_MOMENTUM = 1e-5, 0.1  # nn.BatchNorm2d's defaults, which rl/impala.py:64-65 takes
 
@@ -479,10 +489,11 @@ class DualHeadNet:
     Encoders: ``impala`` (3x3 conv stacks, uint8 or float images; encoder arguments ``channels``, ``n_block`` and
     ``down_sample`` = 'pool' | 'stride' | 'none', see ImpalaSpec, and ``batch_norm``: bn0 / bn1 in every residual block,
     op-by-op launches in exact float32, the mode switched by train() / eval() - see `training`), ``nature`` (three strided convolutions and a linear
-    layer, uint8 or float images; op-by-op launches in exact float32 whatever `precision`), ``rtg`` (a 4x4 stride-2 and
+    layer, uint8 or float images; op-by-op launches, the convolution passes listed in NATURE_SPLIT as split-bf16 launches
+    under `precision` low | medium and everything in exact float32 under high), ``rtg`` (a 4x4 stride-2 and
     two 3x3 convolutions, each behind a fused 2x2 max-pool + ReLU launch, and a linear layer, torch's default
     initialisation; uint8 or float images of at least 18x18, every encoder argument ignored; op-by-op in exact float32
-    like nature) and ``mlp`` (flat float observations);
+    whatever `precision`) and ``mlp`` (flat float observations);
     encoder activation ``relu`` (fused into the head GEMM's operand load) or ``tanh``.  All heads are ONE
     [nh, hidden] matrix so a forward is one GEMM: columns [policy nA | value VH | advantage nA | tvf K*VH].
     """
@@ -617,15 +628,19 @@ class DualHeadNet:
             self.b_heads = self.g_b_heads = None
 
     def _build_split_bf16(self, precision):
-        """--precision=low|medium (rl train.py:166-178 lets cuDNN use TF32 there): the residual blocks of the 32-channel
+        """--precision=low|medium (rl train.py:166-178 lets cuDNN use TF32 there).  nature: the convolution passes listed in
+        NATURE_SPLIT run as split-bf16 launches (csrc/conv_strided_bf16x3.hip), which split their float32 operands
+        themselves - no buffers, no packing jobs.  impala (two blocks, no batch norm): the residual blocks of the 32-channel
         stacks run as split-bf16 launches (csrc/stack_bf16x3.hip: three bf16 MFMAs per product, float32 accumulation,
         ~16-bit products; forward and backward-data).  `high` - the default of this class, of bench.py and of every
         parity test - is exact float32 everywhere.  Buffers: per such stack the forward and the transposed packing of
         its four block convolutions, refreshed by ONE launch behind the float32 re-pack."""
         self.precision = precision
         self.split_bf16, self._pk16, self._split_jobs, self._split_conv_jobs = False, {}, None, None
+        self._nature_split = NATURE_SPLIT if precision != "high" and self.encoder_kind == "nature" else frozenset()
+        self.split_bf16 = bool(self._nature_split)
         if precision == "high" or self.encoder_kind != "impala" or self.spec.n_block != 2 or self.batch_norm:
-            return  # (a batch-norm net runs op by op in exact float32 whatever `precision`, like nature and rtg)
+            return  # (a batch-norm net runs op by op in exact float32 whatever `precision`, like rtg)
         jobs = []
         nbytes = int(self.lib.ppo_impala_stack_tail_bf16x3_packed_bytes())
         for si, (_cin, cout, _h, _w, ho, wo) in enumerate(self.spec.stacks):
@@ -866,7 +881,7 @@ class DualHeadNet:
 
     def mark_weights_changed(self):
         """Call after writing convolution weights other than through adam_step / load_state_dict."""
-        self._packed_dirty = self._pack_table is not None or getattr(self, "split_bf16", False)
+        self._packed_dirty = self._pack_table is not None or getattr(self, "_split_jobs", None) is not None
 
     def _refresh_packed(self):
         if self._packed_dirty:
@@ -874,7 +889,7 @@ class DualHeadNet:
             with self._unrecorded():  # never part of a recorded forward: the refresh is conditional
                 if self._pack_table is not None:
                     self._call("ppo_conv3x3_pack_weights_f32", ctypes.addressof(self._pack_table), len(self._pack_table))
-                if self.split_bf16:
+                if self._split_jobs is not None:
                     self._call("ppo_impala_stack_tail_pack_bf16x3_jobs", ctypes.addressof(self._split_jobs), len(self._split_jobs))
                     if self._split_conv_jobs is not None:
                         self._call("ppo_conv3x3_pack_bf16x3_jobs", ctypes.addressof(self._split_conv_jobs), len(self._split_conv_jobs))
@@ -1069,16 +1084,22 @@ class DualHeadNet:
         self._linear(a1, sp.hidden_units, "encoder.fc2", h, tag=tag)
         return {"x": x, "a1": a1, "h": h}
 
+    def _nature_conv(self, layer, conv_pass):
+        """The entry point of one pass of a Nature layer: split-bf16 for the pairs of NATURE_SPLIT under precision
+        low | medium, else exact float32."""
+        return f"ppo_conv2d_strided_{conv_pass}_" + ("bf16x3" if (layer, conv_pass) in self._nature_split else "f32")
+
     def _encode_nature(self, x, train, tag, tail):
         """NatureCNN.forward (rl/models.py:130-145), one launch per layer: three strided convolutions with the ReLU in
-        their stores, then the linear layer - with the heads (and the action step or the PPO loss) in the same call when
-        the encoder activation is relu, as behind the IMPALA encoder."""
+        their stores (exact float32, or split-bf16 where _nature_conv says so), then the linear layer - with the heads
+        (and the action step or the PPO loss) in the same call when the encoder activation is relu, as behind the
+        IMPALA encoder."""
         sp, B = self.spec, x.shape[0]
         acts = {"x": x}
         cur, mode = x, (IN_U8 if x.dtype == torch.uint8 else IN_NONE)
         for name, cin, cout, k, s, h, w, ho, wo in sp.layers:
             y = self._buf(f"{tag}{name}", (B, cout, ho, wo))
-            self._call("ppo_conv2d_strided_forward_f32", _p(cur), mode, _p(self.params[f"encoder.{name}.weight"]),
+            self._call(self._nature_conv(name, "forward"), _p(cur), mode, _p(self.params[f"encoder.{name}.weight"]),
                        _p(self.params[f"encoder.{name}.bias"]), _p(y), 1, B, cin, h, w, cout, k, k, s)
             acts[name] = y
             cur, mode = y, IN_NONE
@@ -1534,7 +1555,8 @@ class DualHeadNet:
         """Backward through the Nature encoder, one launch per gradient: the linear layer (its data gradient gated by
         conv3's output, i.e. already through conv3's ReLU), then weight and data gradients of conv3 and conv2 and the
         weight gradient of conv1 - nothing back-propagates into the observations.  Each strided-convolution launch
-        takes the gradient w.r.t. its layer's post-ReLU output and gates it by that output itself."""
+        takes the gradient w.r.t. its layer's post-ReLU output and gates it by that output itself; the passes listed
+        in NATURE_SPLIT are split-bf16 launches under precision low | medium (same arguments, same workspace)."""
         sp = self.spec
         B = dh.shape[0]
         x, flat = acts["x"], acts["flat"]
@@ -1548,11 +1570,11 @@ class DualHeadNet:
             geom = (B, cin, h, w, cout, k, k, s)
             nbytes = int(self.lib.ppo_conv2d_strided_wgrad_workspace_bytes(*geom))
             ws = self._ws("nwgrad_ws_" + name, nbytes)
-            self._call("ppo_conv2d_strided_backward_weight_f32", _p(src), mode, _p(g), _p(gate),
+            self._call(self._nature_conv(name, "backward_weight"), _p(src), mode, _p(g), _p(gate),
                        _p(self.grads[f"encoder.{name}.weight"]), _p(self.grads[f"encoder.{name}.bias"]), _p(ws), nbytes, *geom)
             if li:
                 gx = self._buf("ng_" + sp.layers[li - 1][0], tuple(src.shape))
-                self._call("ppo_conv2d_strided_backward_data_f32", _p(g), _p(gate), _p(self.params[f"encoder.{name}.weight"]),
+                self._call(self._nature_conv(name, "backward_data"), _p(g), _p(gate), _p(self.params[f"encoder.{name}.weight"]),
                            _p(gx), *geom)
                 g, gate = gx, src
         if self.grad_ready_hook is not None:
