@@ -10,14 +10,17 @@ namespace ppo {
 constexpr int kMaxActions = 32;
 
 // counter-based uniform in (0, 1): 2 rounds of a 64-bit mix (splitmix64 finaliser) of
-// (seed, counter); 24 mantissa bits, never 0 or 1 so that log(-log u) is finite.
+// (seed, counter); k = the top 24 bits, u = (k + 0.5) 2^-24 rounded to float32 and clamped to 1 - 2^-24.  k + 0.5 is
+// no float32 for k >= 2^23 (it rounds to even), so without the clamp k = 2^24 - 1 gave u == 1.0f: log(-log u) = -inf
+// and the Gumbel score +inf, that action taken whatever its probability (once per 2^24 draws).  The clamp changes that
+// one value only - every other draw keeps its bits - and u stays strictly inside (0, 1): log(-log u) is finite.
 __device__ __forceinline__ float uniform01(uint64_t seed, uint64_t counter)
 {
     uint64_t z = seed + 0x9E3779B97F4A7C15ull * (counter + 1);
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
     z = z ^ (z >> 31);
-    return ((float)(z >> 40) + 0.5f) * (1.0f / 16777216.0f);
+    return fminf(((float)(z >> 40) + 0.5f) * (1.0f / 16777216.0f), 0x1.fffffep-1f);
 }
 
 struct ActOut {
