@@ -97,6 +97,11 @@ int ppo_bootstrapped_returns_f32(const float *rewards, const void *dones, int do
 #define PPO_IN_NONE 0 /* float32 input used as is */
 #define PPO_IN_RELU 1 /* float32 input, max(x, 0) applied on load (pre-activation blocks, rl/impala.py:73-78) */
 #define PPO_IN_U8 2   /* uint8 observation, x / 255 applied on load (rl/models.py:842-848, "scaled") */
+/* The signed preparations (--observation_scaling, rl/models.py:846-855), accepted wherever PPO_IN_U8 is: the same bytes,
+ * the same kernels, each float32 operation rounded on its own as torch rounds it.  Padding taps and padded channels
+ * contribute exactly 0.0f, not f(0). */
+#define PPO_IN_U8_CENTERED 4 /* x / 255 - 0.5 */
+#define PPO_IN_U8_UNIT 5     /* (x / 255 - 0.5) * 6      (3 is no mode) */
 
 /*
  * out[n,o,y,x] = bias[o] + sum_{i,ky,kx} f(in[n,i,y+ky-1,x+kx-1]) * weight[o,i,ky,kx] (+ residual[n,o,y,x])
@@ -815,7 +820,13 @@ int ppo_impala_stack_full_forward_f32(const float *in, const float *const *packe
  *                          (the caller adds batch_count afterwards).  Also refreshes the float32 constants
  *                          mu = mean, std = sqrt(float32(var))  (refresh_normalization_constants, :661-663).
  * ppo_obs_normalize_f32:   out [B, F] float32; bit-identical to the torch expression at :692.
- * ---------------------------------------------------------------------- */
+ * ----------------------------------------------------------------------
+ * is_u8 names the preparation of x: PPO_OBS_F32 (float32 as is), PPO_OBS_U8 (uint8, x/255), PPO_OBS_U8_CENTERED (uint8,
+ * x/255 - 0.5), PPO_OBS_U8_UNIT (uint8, (x/255 - 0.5) * 6): the three values of --observation_scaling, rl/models.py:846-855. */
+#define PPO_OBS_F32 0
+#define PPO_OBS_U8 1
+#define PPO_OBS_U8_CENTERED 2
+#define PPO_OBS_U8_UNIT 3
 int ppo_obs_moments_f64(const void *x, int is_u8, int B, int F, double *moments, void *stream);
 int ppo_obs_rms_update_f64(const double *moments, double batch_count, double count, double *mean, double *var,
                            float *mu, float *std, int F, void *stream);
@@ -881,6 +892,11 @@ int ppo_rnd_error_f32(const float *pred, const float *target, int B, int F, floa
 #define PPO_HASH_RAW_CENTERED 1
 #define PPO_HASH_NORMED 2
 #define PPO_HASH_NORMED_OFFSET 3
+/* _NORMED / _NORMED_OFFSET on the signed preparations of the byte: o/255 - 0.5 and (o/255 - 0.5) * 6 in place of o/255 */
+#define PPO_HASH_NORMED_CENTERED 8
+#define PPO_HASH_NORMED_OFFSET_CENTERED 9
+#define PPO_HASH_NORMED_UNIT 10
+#define PPO_HASH_NORMED_OFFSET_UNIT 11
 #define PPO_HASH_BONUS_HYPERBOLIC 0
 #define PPO_HASH_BONUS_QUADRATIC 1
 #define PPO_HASH_BONUS_BINARY 2

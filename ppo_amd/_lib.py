@@ -18,8 +18,11 @@ LIB_PATH = os.environ.get("PPO_AMD_LIB") or os.path.join(HERE, "lib", "libppo_am
 PPO_TERM_NONE, PPO_TERM_U8, PPO_TERM_F32 = 0, 1, 2
 PPO_SCAN_AUTO, PPO_SCAN_COLUMNS, PPO_SCAN_TILES = 0, 1, 2
 PPO_IN_NONE, PPO_IN_RELU, PPO_IN_U8 = 0, 1, 2
+PPO_IN_U8_CENTERED, PPO_IN_U8_UNIT = 4, 5  # the signed uint8 preparations, accepted wherever PPO_IN_U8 is (3 is no mode)
+PPO_OBS_F32, PPO_OBS_U8, PPO_OBS_U8_CENTERED, PPO_OBS_U8_UNIT = 0, 1, 2, 3  # `is_u8` of the ppo_obs_* entry points
 PPO_RND_STATS = 5
 PPO_HASH_RAW, PPO_HASH_RAW_CENTERED, PPO_HASH_NORMED, PPO_HASH_NORMED_OFFSET = 0, 1, 2, 3
+PPO_HASH_NORMED_CENTERED, PPO_HASH_NORMED_OFFSET_CENTERED, PPO_HASH_NORMED_UNIT, PPO_HASH_NORMED_OFFSET_UNIT = 8, 9, 10, 11
 PPO_HASH_BONUS_HYPERBOLIC, PPO_HASH_BONUS_QUADRATIC, PPO_HASH_BONUS_BINARY = 0, 1, 2
 PPO_REPLAY_AUX_FLOATS, PPO_REPLAY_MAX_PAIRWISE_ROWS = 16, 128
 

@@ -456,7 +456,9 @@ class Config:
         a("--observation_normalization", type=str2bool, nargs="?", const=True, default=False)
         a("--observation_normalization_epsilon", type=float, default=0.003)
         a("--freeze_observation_normalization", type=str2bool, nargs="?", const=True, default=False)
-        a("--observation_scaling", type=str, default="scaled")
+        a("--observation_scaling", type=str, default="scaled",
+          help="[scaled|centered|unit] (rl/models.py:846-855) what a uint8 observation becomes: x/255, x/255 - 0.5 or "
+               "(x/255 - 0.5) * 6, applied in the load of the kernels that read it; float32 observations are used as they are")
         a("--seed", type=int, default=self.seed)
         a("--epochs", type=float, default=self.epochs, help="millions of env steps to train for")
         a("--limit_epochs", type=float, default=None)
@@ -532,6 +534,8 @@ class Config:
             raise ValueError(f"Invalid distil target {self.distil.target}")
         if self.distil.value_loss not in DistilConfig.VALUE_LOSSES:
             raise ValueError(f"Invalid loss distil loss {self.distil.value_loss}")
+        if self.observation_scaling not in ("scaled", "centered", "unit"):  # the model's own refusal (rl/models.py:855)
+            raise ValueError(f"Invalid observation_scaling mode {self.observation_scaling}")
         if self.distil.delta < 0:
             raise ValueError(f"--distil_delta={self.distil.delta} must be >= 0")
         if self.rnd.enabled:

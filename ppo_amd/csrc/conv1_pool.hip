@@ -85,7 +85,7 @@ __device__ __forceinline__ void columns_max(HRow &r)
     }
 }
 
-template <int H, int W, bool TRAIN, bool PACKED>
+template <int H, int W, bool TRAIN, bool PACKED, int IN_MODE>
 __global__ __launch_bounds__(64) void conv1_pool_kernel(const uint8_t *__restrict__ in, const int32_t *__restrict__ in_index,
                                                         const float *__restrict__ w, const float *__restrict__ bias,
                                                         float *__restrict__ out, uint8_t *__restrict__ argmax, int n_images,
@@ -121,7 +121,7 @@ __global__ __launch_bounds__(64) void conv1_pool_kernel(const uint8_t *__restric
     float bias_r[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) bias_r[i] = bias ? bias[4 * g + i] : 0.f;
-    // Tame parameters (every |w|, |b| <= 1e30: inputs are in [0, 1], 36 products per output) cannot produce a non-finite
+    // Tame parameters (every |w|, |b| <= 1e30: inputs are in [0, 1] - [-3, 3] at most under the signed preparations -, 36 products per output) cannot produce a non-finite
     // output, so the walk does not look for one; otherwise every window of the strip goes through the reference scan.
     bool tame = true;
 #pragma unroll
@@ -156,15 +156,29 @@ __global__ __launch_bounds__(64) void conv1_pool_kernel(const uint8_t *__restric
 #endif
         xo[t] = 7 * (2 * pair + t) + (l15 >> 1);
     }
+    // signed preparations: f(0) != 0, so the bytes that stand for columns -1 and W must be told from pixels
+    bool colok[2][3];
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const int x = 14 * (2 * pair + t) - 1 + l15 - 1 + j;
+            colok[t][j] = x >= 0 && x < W;
+        }
     auto fetch = [&](int t, int y) -> uint32_t {  // y is wave-uniform; rows outside the image read as zeros
         const bool ok = y >= 0 && y < H;
         return (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rin, ok ? voff[t] : kOutside, ok ? y * W : 0, 0);
     };
-    auto unpack = [&](int t, uint32_t d, float (&x)[3]) {
+    auto unpack = [&](int t, uint32_t d, float (&x)[3], int y) {  // y: the row `d` was fetched from (wave-uniform)
         const uint32_t v = (d << shl[t]) >> shr[t];
-        x[0] = u8_unit((float)(v & 0xffu));
-        x[1] = u8_unit((float)((v >> 8) & 0xffu));
-        x[2] = u8_unit((float)((v >> 16) & 0xffu));
+        x[0] = u8_prep<IN_MODE>((float)(v & 0xffu));
+        x[1] = u8_prep<IN_MODE>((float)((v >> 8) & 0xffu));
+        x[2] = u8_prep<IN_MODE>((float)((v >> 16) & 0xffu));
+        if constexpr (in_mode_is_signed_u8(IN_MODE)) {  // padding is 0.0f, not f(0)
+            const bool rowok = y >= 0 && y < H;
+#pragma unroll
+            for (int j = 0; j < 3; ++j) x[j] = (rowok && colok[t][j]) ? x[j] : 0.f;
+        }
     };
 
     // output: lane (odd l15 <= 13, g) stores channels 4 g .. 4 g + 3 of pooled column xo; the others are out of range
@@ -194,9 +208,9 @@ __global__ __launch_bounds__(64) void conv1_pool_kernel(const uint8_t *__restric
         const uint32_t d0 = fetch(t, ys - 1), d1 = fetch(t, ys), d2 = fetch(t, ys + 1);
         pend0[t] = fetch(t, ys + 2);
         pend1[t] = fetch(t, ys + 3);
-        unpack(t, d0, xw[t][0]);
-        unpack(t, d1, xw[t][1]);
-        unpack(t, d2, xw[t][2]);
+        unpack(t, d0, xw[t][0], ys - 1);
+        unpack(t, d1, xw[t][1], ys);
+        unpack(t, d2, xw[t][2], ys + 1);
     }
     int ynext = ys + 4;
 
@@ -232,7 +246,7 @@ __global__ __launch_bounds__(64) void conv1_pool_kernel(const uint8_t *__restric
         columns_max<TRAIN, KB>(r[1]);
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
-            unpack(t, pend0[t], xw[t][PH]);
+            unpack(t, pend0[t], xw[t][PH], ynext - 3);  // pend0 / pend1 / newd: rows ynext - 3, - 2, - 1 (ynext counted above)
             pend0[t] = pend1[t];
             pend1[t] = newd[t];
         }
@@ -320,7 +334,7 @@ __global__ __launch_bounds__(64) void conv1_pool_kernel(const uint8_t *__restric
     }
 }
 
-template <int H, int W, bool TRAIN, bool PACKED>
+template <int H, int W, bool TRAIN, bool PACKED, int IN_MODE>
 int launch_conv1(const void *in, const int32_t *in_index, const float *w, const float *bias, float *out, uint8_t *argmax,
                  int n, int cin, hipStream_t st)
 {
@@ -335,7 +349,7 @@ int launch_conv1(const void *in, const int32_t *in_index, const float *w, const 
     const long n_tasks = (long)n * NPAIR * nstrip;
     const long grid = (n_tasks + 7) / 8 * 8;
     if (grid > 0x7fffffffL) return fail(PPO_E_INVALID, "conv1_pool: %d images are too many strips for one launch", n);
-    hipLaunchKernelGGL((conv1_pool_kernel<H, W, TRAIN, PACKED>), dim3((unsigned)grid), dim3(64), 0, st,
+    hipLaunchKernelGGL((conv1_pool_kernel<H, W, TRAIN, PACKED, IN_MODE>), dim3((unsigned)grid), dim3(64), 0, st,
                        static_cast<const uint8_t *>(in), in_index, w, bias, out, argmax, n, cin, prs, nstrip);
     return check_launch("conv1_pool_kernel");
 }
@@ -359,21 +373,28 @@ bool conv1_pool_supported(int cin, int cout, int h, int w, bool train)
     return can && g_form == 0;
 }
 
+template <int IN_MODE>
 int conv1_pool_forward(const void *in, const int32_t *in_index, const float *w, bool packed, const float *bias, float *out,
                        uint8_t *argmax, int n, int cin, int h, int w_, hipStream_t st)
 {
 #define PPO_C1(HH)                                                                                                      \
     if (h == HH && w_ == HH) {                                                                                          \
         if (argmax)                                                                                                     \
-            return packed ? launch_conv1<HH, HH, true, true>(in, in_index, w, bias, out, argmax, n, cin, st)            \
-                          : launch_conv1<HH, HH, true, false>(in, in_index, w, bias, out, argmax, n, cin, st);          \
-        return packed ? launch_conv1<HH, HH, false, true>(in, in_index, w, bias, out, argmax, n, cin, st)               \
-                      : launch_conv1<HH, HH, false, false>(in, in_index, w, bias, out, argmax, n, cin, st);             \
+            return packed ? launch_conv1<HH, HH, true, true, IN_MODE>(in, in_index, w, bias, out, argmax, n, cin, st)            \
+                          : launch_conv1<HH, HH, true, false, IN_MODE>(in, in_index, w, bias, out, argmax, n, cin, st);          \
+        return packed ? launch_conv1<HH, HH, false, true, IN_MODE>(in, in_index, w, bias, out, argmax, n, cin, st)               \
+                      : launch_conv1<HH, HH, false, false, IN_MODE>(in, in_index, w, bias, out, argmax, n, cin, st);             \
     }
     PPO_C1(84)
 #undef PPO_C1
     return fail(PPO_E_INVALID, "conv1_pool: unsupported geometry h=%d w=%d", h, w_);
 }
+template int conv1_pool_forward<IN_U8>(const void *, const int32_t *, const float *, bool, const float *, float *, uint8_t *, int, int,
+                                       int, int, hipStream_t);
+template int conv1_pool_forward<IN_U8_CENTERED>(const void *, const int32_t *, const float *, bool, const float *, float *, uint8_t *,
+                                                int, int, int, int, hipStream_t);
+template int conv1_pool_forward<IN_U8_UNIT>(const void *, const int32_t *, const float *, bool, const float *, float *, uint8_t *, int,
+                                            int, int, int, hipStream_t);
 
 }  // namespace ppo
 

@@ -36,6 +36,7 @@ namespace ppo {
 
 // conv1_pool.hip: the first layer on uint8 observations, pooled out of the MFMA accumulators
 bool conv1_pool_supported(int cin, int cout, int h, int w, bool train);
+template <int IN_MODE>
 int conv1_pool_forward(const void *in, const int32_t *in_index, const float *w, bool packed, const float *bias, float *out,
                        uint8_t *argmax, int n, int cin, int h, int w_, hipStream_t st);
 
@@ -153,7 +154,7 @@ __global__ __launch_bounds__(NW * 64) void conv3x3_kernel(
     const float *__restrict__ residual, const float *__restrict__ mask_src, float *__restrict__ out,
     int n_images)
 {
-    constexpr bool DMA = IN_MODE != IN_U8;
+    constexpr bool DMA = !in_mode_is_u8(IN_MODE);
     constexpr int kConvWaves = NW, kConvThreads = NW * 64;
     using C = ConvCfg<CIN, COUT, H, W, TR, DMA>;
     extern __shared__ __align__(16) float smem[];
@@ -543,7 +544,7 @@ __global__ __launch_bounds__(NW * 64) void conv3x3_kernel(
 template <int CIN, int COUT, int H, int W, int TR, int MT, int NW, int IN_MODE, bool TRANSPOSED, bool PACKED, bool WIDE>
 int launch_conv_impl(const ConvArgs &a)
 {
-    using C = ConvCfg<CIN, COUT, H, W, TR, IN_MODE != IN_U8>;
+    using C = ConvCfg<CIN, COUT, H, W, TR, !in_mode_is_u8(IN_MODE)>;
     constexpr auto kern = conv3x3_kernel<CIN, COUT, H, W, TR, MT, NW, IN_MODE, TRANSPOSED, PACKED, WIDE>;
     constexpr int kConvThreads = NW * 64;
     // the band buffers (+ the WIDE epilogue's per-wave scratch), or the padded weight image the prologue stages
@@ -571,7 +572,7 @@ template <int CIN, int COUT, int H, int W, int TR, int MT, int NW, int IN_MODE, 
 int launch_conv(const ConvArgs &a)
 {
     // the 16-byte epilogue needs whole float4s: channel planes and bands a multiple of 4 floats, 16-byte aligned tensors
-    constexpr bool kWideGeo = (H * W) % 4 == 0 && (TR * W) % 4 == 0 && IN_MODE != IN_U8;
+    constexpr bool kWideGeo = (H * W) % 4 == 0 && (TR * W) % 4 == 0 && !in_mode_is_u8(IN_MODE);
 #ifdef PPO_TUNE_NO_WIDE
     const bool wide = false;
 #else
@@ -609,7 +610,7 @@ int dispatch_conv(int cin, int cout, int h, int w_, const ConvArgs &a)
     constexpr bool FIRST = !TRANSPOSED && IN_MODE != IN_RELU;
     constexpr bool UP = !TRANSPOSED && IN_MODE == IN_NONE;
     constexpr bool DOWN = TRANSPOSED;
-    constexpr bool SAME = IN_MODE != IN_U8;
+    constexpr bool SAME = !in_mode_is_u8(IN_MODE);
     PPO_CONV_CASE(FIRST, 4, 16, 84, 84, 12, 4, 8)   // 63 tiles -> 16 groups of 4: 2 per wave
     PPO_CONV_CASE(FIRST, 5, 16, 84, 84, 12, 4, 8)
     PPO_CONV_CASE(FIRST, 3, 16, 64, 64, 16, 4, 8)   // 64 tiles -> 16 groups
@@ -668,7 +669,7 @@ __global__ __launch_bounds__(NW * 64) void conv3x3_pool_kernel(const void *__res
                                                               uint8_t *__restrict__ argmax, int n_images,
                                                               const int32_t *__restrict__ in_index)
 {
-    constexpr bool DMA = IN_MODE != IN_U8;
+    constexpr bool DMA = !in_mode_is_u8(IN_MODE);
     constexpr int kWaves = NW, kThreads = NW * 64;
     using C = ConvPoolCfg<CIN, COUT, H, W, PR, DMA>;
     extern __shared__ __align__(16) float smem[];
@@ -739,7 +740,7 @@ __global__ __launch_bounds__(NW * 64) void conv3x3_pool_kernel(const void *__res
     if (DMA && (int)blockIdx.x < n_items) stage(blockIdx.x, smem);
     // uint8 observations: the next item's band waits in registers while this item computes (four pixels per
     // register where the row length allows dword loads)
-    constexpr bool U8X4 = !DMA && IN_MODE == IN_U8 && W % 4 == 0;
+    constexpr bool U8X4 = !DMA && in_mode_is_u8(IN_MODE) && W % 4 == 0;
     using FM = FlatMap<C::CINP, W, C::ROWS, kWaves>;
     using FM4 = FlatU8Map<CIN, (U8X4 ? W : 4), C::ROWS, kThreads>;
     uint32_t raw[DMA ? 1 : (U8X4 ? FM4::Q : FM::Q)];
@@ -770,7 +771,7 @@ __global__ __launch_bounds__(NW * 64) void conv3x3_pool_kernel(const void *__res
             if (item + (int)gridDim.x < n_items) stage(item + gridDim.x, smem + (buf ^ 1) * C::LDS_IN);
         } else {
             __syncthreads();  // previous item's readers are done with the band and s_out
-            if constexpr (U8X4) band_u8x4_store<CIN, W, C::ROWS, C::PLANE, C::G, kThreads>(raw, smem, tid);
+            if constexpr (U8X4) band_u8x4_store<CIN, W, C::ROWS, C::PLANE, C::G, kThreads, IN_MODE, H>(raw, smem, tid, 2 * yo0 - 1);
             else band_flat_store<C::CINP, W, C::ROWS, C::PLANE, C::G, IN_MODE, kWaves>(raw, smem, tid);
             if (item + (int)gridDim.x < n_items) prefetch(item + gridDim.x);
             __syncthreads();
@@ -919,7 +920,7 @@ __global__ __launch_bounds__(NW * 64) void conv3x3_pool_kernel(const void *__res
 template <int CIN, int COUT, int H, int W, int PR, int MT, int NW, int IN_MODE, bool PACKED>
 int launch_conv_pool_impl(const ConvArgs &a)
 {
-    using C = ConvPoolCfg<CIN, COUT, H, W, PR, IN_MODE != IN_U8>;
+    using C = ConvPoolCfg<CIN, COUT, H, W, PR, !in_mode_is_u8(IN_MODE)>;
     constexpr auto kern = conv3x3_pool_kernel<CIN, COUT, H, W, PR, MT, NW, IN_MODE, PACKED>;
     constexpr size_t kWeightImage = (size_t)COUT * ((CIN * 9) | 1) * 4;
     constexpr size_t kLdsBytes = C::LDS_BYTES > kWeightImage ? C::LDS_BYTES : kWeightImage;
@@ -960,10 +961,10 @@ int dispatch_conv_pool(int cin, int cout, int h, int w_, const ConvArgs &a)
         }                                                                     \
     }
     constexpr bool FLOAT = IN_MODE == IN_NONE;
-    if constexpr (IN_MODE == IN_U8) {
+    if constexpr (in_mode_is_u8(IN_MODE)) {
         // (a geometry of the list below: a probe finds it there)
         if (!a.probe && conv1_pool_supported(cin, cout, h, w_, a.argmax != nullptr))
-            return conv1_pool_forward(a.in, a.in_index, a.w, a.packed, a.bias, a.out, a.argmax, a.n, cin, h, w_, a.st);
+            return conv1_pool_forward<IN_MODE>(a.in, a.in_index, a.w, a.packed, a.bias, a.out, a.argmax, a.n, cin, h, w_, a.st);
     }
 #ifndef PPO_CP_PR84  // 84x84 first layer: pooled rows per item / pixel tiles per wave group
 #define PPO_CP_PR84 3   // 7 rows x 84 = 37 tiles -> 8 groups of 5; 51 KB of LDS: three workgroups per CU
@@ -1021,7 +1022,7 @@ int conv_backward_data(const char *who, bool packed, const float *dy, const floa
 int conv_pool_forward(const char *who, bool packed, const void *in, const int32_t *index, int in_mode, const float *weight,
                       const float *bias, float *out, uint8_t *argmax, int n, int cin, int cout, int h, int w, void *stream)
 {
-    if (index && in_mode != IN_U8) return fail(PPO_E_INVALID, "%s: the index applies to uint8 observations", who);
+    if (index && !in_mode_is_u8(in_mode)) return fail(PPO_E_INVALID, "%s: the index applies to uint8 observations", who);
     if (n < 0) return fail(PPO_E_INVALID, "%s: n < 0", who);
     if (n == 0) return PPO_OK;
     if (!in || !weight || !out) return fail(PPO_E_INVALID, "%s: null pointer", who);

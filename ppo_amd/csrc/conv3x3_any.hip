@@ -30,7 +30,7 @@ using tile::kTK;
 
 __device__ __forceinline__ float load_in(const void *in, int in_mode, long long off)
 {
-    if (in_mode == IN_U8) return u8_unit((float)static_cast<const uint8_t *>(in)[off]);
+    if (in_mode_is_u8(in_mode)) return u8_prep((float)static_cast<const uint8_t *>(in)[off], in_mode);
     const float v = static_cast<const float *>(in)[off];
     return in_mode == IN_RELU ? fmaxf(v, 0.0f) : v;
 }
@@ -296,7 +296,7 @@ extern "C" int ppo_conv3x3_any_forward_f32(const void *in, int in_mode, const fl
     c3i::Geom g;
     if (int rc = check_geometry(what, n, cin, cout, h, w, &g)) return rc;
     if (in == nullptr || weight == nullptr || out == nullptr) return fail(PPO_E_INVALID, "%s: null pointer", what);
-    if (in_mode != IN_NONE && in_mode != IN_RELU && in_mode != IN_U8) return fail(PPO_E_INVALID, "%s: unknown in_mode %d", what, in_mode);
+    if (in_mode != IN_NONE && in_mode != IN_RELU && !in_mode_is_u8(in_mode)) return fail(PPO_E_INVALID, "%s: unknown in_mode %d", what, in_mode);
     ForwardOp op{g, in, in_mode, weight, bias, residual, out, c3i::pix_m(g), cout, c3i::fwd_k(g)};
     hipLaunchKernelGGL(conv_gemm_kernel<ForwardOp>, gemm_grid(op.M, op.N, 1), dim3(kThreads), 0, as_stream(stream), op);
     return check_launch(what);
@@ -333,7 +333,7 @@ extern "C" int ppo_conv3x3_any_backward_weight_f32(const void *in, int in_mode, 
     if (int rc = check_geometry(what, n, cin, cout, h, w, &g)) return rc;
     if (in == nullptr || dy == nullptr || dweight == nullptr || workspace == nullptr)
         return fail(PPO_E_INVALID, "%s: null pointer", what);
-    if (in_mode != IN_NONE && in_mode != IN_RELU && in_mode != IN_U8) return fail(PPO_E_INVALID, "%s: unknown in_mode %d", what, in_mode);
+    if (in_mode != IN_NONE && in_mode != IN_RELU && !in_mode_is_u8(in_mode)) return fail(PPO_E_INVALID, "%s: unknown in_mode %d", what, in_mode);
     int rows;
     const int slabs = wgrad_slabs(g, &rows);
     const int K = c3i::fwd_k(g);
@@ -361,7 +361,7 @@ extern "C" int ppo_conv3x3s2_any_forward_f32(const void *in, int in_mode, const 
     c3s::Geom g;
     if (int rc = check_geometry_s2(what, n, cin, cout, h, w, &g)) return rc;
     if (in == nullptr || weight == nullptr || out == nullptr) return fail(PPO_E_INVALID, "%s: null pointer", what);
-    if (in_mode != IN_NONE && in_mode != IN_RELU && in_mode != IN_U8) return fail(PPO_E_INVALID, "%s: unknown in_mode %d", what, in_mode);
+    if (in_mode != IN_NONE && in_mode != IN_RELU && !in_mode_is_u8(in_mode)) return fail(PPO_E_INVALID, "%s: unknown in_mode %d", what, in_mode);
     S2ForwardOp op{g, in, in_mode, weight, bias, residual, out, c3s::fwd_m(g), cout, c3s::fwd_k(g)};
     hipLaunchKernelGGL(conv_gemm_kernel<S2ForwardOp>, gemm_grid(op.M, op.N, 1), dim3(kThreads), 0, as_stream(stream), op);
     return check_launch(what);
@@ -399,7 +399,7 @@ extern "C" int ppo_conv3x3s2_any_backward_weight_f32(const void *in, int in_mode
     if (int rc = check_geometry_s2(what, n, cin, cout, h, w, &g)) return rc;
     if (in == nullptr || dy == nullptr || dweight == nullptr || workspace == nullptr)
         return fail(PPO_E_INVALID, "%s: null pointer", what);
-    if (in_mode != IN_NONE && in_mode != IN_RELU && in_mode != IN_U8) return fail(PPO_E_INVALID, "%s: unknown in_mode %d", what, in_mode);
+    if (in_mode != IN_NONE && in_mode != IN_RELU && !in_mode_is_u8(in_mode)) return fail(PPO_E_INVALID, "%s: unknown in_mode %d", what, in_mode);
     int rows;
     const int slabs = wgrad_slabs_s2(g, &rows);
     const int K = c3s::fwd_k(g);

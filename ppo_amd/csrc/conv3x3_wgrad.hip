@@ -57,7 +57,7 @@ constexpr int pad_mod32(int v, int target) { return v + ((target - v % 32) + 32)
 template <int IN_MODE, int NBANDS>
 constexpr int wgrad_nbuf()
 {
-    return IN_MODE == IN_U8 ? 1 : (NBANDS == 1 ? PPO_TUNE_WGRAD_NBUF_ONEBAND : PPO_TUNE_WGRAD_NBUF);
+    return in_mode_is_u8(IN_MODE) ? 1 : (NBANDS == 1 ? PPO_TUNE_WGRAD_NBUF_ONEBAND : PPO_TUNE_WGRAD_NBUF);
 }
 // contiguous-run band layout (16-byte LDS-DMA) wherever both bands arrive by DMA
 template <int IN_MODE, bool DY_POOLED>
@@ -77,7 +77,7 @@ constexpr int kWgradWaves = 8;
 template <int IN_MODE, int NBANDS, bool DY_POOLED>
 constexpr bool wgrad_dma_wave()
 {
-    return PPO_TUNE_WGRAD_DMA_WAVE && wgrad_nbuf<IN_MODE, NBANDS>() == 2 && IN_MODE != IN_U8 && !DY_POOLED;
+    return PPO_TUNE_WGRAD_DMA_WAVE && wgrad_nbuf<IN_MODE, NBANDS>() == 2 && !in_mode_is_u8(IN_MODE) && !DY_POOLED;
 }
 constexpr int kWgradDmaWaves = PPO_TUNE_WGRAD_DMA_WAVE;  // staging waves (0 = the compute waves stage)
 template <int IN_MODE, int NBANDS, bool DY_POOLED>
@@ -284,11 +284,11 @@ __global__ __launch_bounds__((wgrad_threads<IN_MODE, (H + TR - 1) / TR, DY_POOLE
         const int img = item / C::NBANDS;
         const int y0 = (item % C::NBANDS) * TR;
         if constexpr (C::RUN) {
-            if constexpr (IN_MODE == IN_U8) {
+            if constexpr (in_mode_is_u8(IN_MODE)) {
                 // uint8 observations: four pixels per lane (dword load, exact x / 255, 16-byte LDS store)
                 uint32_t raw[FlatU8Map<CIN, W, C::ROWS, kWgradWaves * 64>::Q];
                 band_u8x4_load<CIN, H, W, C::ROWS, kWgradWaves * 64>(in_, batch.in_index ? batch.in_index[img] : img, y0, tid, raw);
-                band_u8x4_store<CIN, W, C::ROWS, C::XPLANE, C::G, kWgradWaves * 64>(raw, bx, tid);
+                band_u8x4_store<CIN, W, C::ROWS, C::XPLANE, C::G, kWgradWaves * 64, IN_MODE, H>(raw, bx, tid, y0);
             } else {
                 stage_band_chunk_dma<CIN, H, W, C::ROWS, C::XPLANE, C::G, SW>(static_cast<const float *>(in_), img, y0, bx, stid);
             }
@@ -300,7 +300,7 @@ __global__ __launch_bounds__((wgrad_threads<IN_MODE, (H + TR - 1) / TR, DY_POOLE
                 stage_band_chunk_dma<COUT, H, W, TR, C::DPLANE, 0, SW>(dy, img, y0 + 1, bd, stid);
             }
             return;
-        } else if constexpr (IN_MODE == IN_U8)
+        } else if constexpr (in_mode_is_u8(IN_MODE))
             stage_band<CIN, C::CINP, H, W, C::ROWS, C::PWX, C::XPLANE, 1, IN_MODE, kWgradWaves>(in_, img, y0, bx, tid);
         else
             stage_band_dma<CIN, H, W, C::ROWS, C::PWX, C::XPLANE, 1, kWgradWaves>(static_cast<const float *>(in_), img, y0, bx, tid);
@@ -344,7 +344,7 @@ __global__ __launch_bounds__((wgrad_threads<IN_MODE, (H + TR - 1) / TR, DY_POOLE
         // Register-staged operands (uint8 observations, the pooled gradient's gather) are fetched for the NEXT item
         // before this item's K loop and written to LDS after it, so their load latency hides under the MFMAs (the
         // single-buffered loop exposed it: staging was 65 % of an item).  DMA-staged operands keep the plain order.
-        constexpr bool PRE_X = C::RUN && IN_MODE == IN_U8, PRE_D = C::RUN && DY_POOLED;
+        constexpr bool PRE_X = C::RUN && in_mode_is_u8(IN_MODE), PRE_D = C::RUN && DY_POOLED;
         using XM = FlatU8Map<CIN, (PRE_X ? W : 4), C::ROWS, kWgradWaves * 64>;
         using DM = PooledMap<COUT, (PRE_D ? H : 2), (PRE_D ? W : 4), (PRE_D ? TR : 2), kWgradWaves>;
         uint32_t xraw[PRE_X ? XM::Q : 1];
@@ -362,7 +362,7 @@ __global__ __launch_bounds__((wgrad_threads<IN_MODE, (H + TR - 1) / TR, DY_POOLE
             PPO_STAMP(t_bar)
             if constexpr (PRE_X || PRE_D) {
                 const int img = item / C::NBANDS, y0 = (item % C::NBANDS) * TR;
-                if constexpr (PRE_X) band_u8x4_store<CIN, W, C::ROWS, C::XPLANE, C::G, kWgradWaves * 64>(xraw, s_x, tid);
+                if constexpr (PRE_X) band_u8x4_store<CIN, W, C::ROWS, C::XPLANE, C::G, kWgradWaves * 64, IN_MODE, H>(xraw, s_x, tid, y0);
                 else stage_band_chunk_dma<CIN, H, W, C::ROWS, C::XPLANE, C::G, kWgradWaves>(static_cast<const float *>(in_), img, y0, s_x, tid);
                 if constexpr (PRE_D) dy_pooled_store<COUT, H, W, TR, C::PWD, C::DPLANE, kWgradWaves>(draw, y0, s_d, tid);
                 else stage_band_chunk_dma<COUT, H, W, TR, C::DPLANE, 0, kWgradWaves>(dy, img, y0 + 1, s_d, tid);
@@ -641,7 +641,7 @@ int launch_wgrad(const WgradArgs &a)
         batch.partial[0] = a.ws;
     }
     batch.argmax = a.argmax;
-    batch.in_index = IN_MODE == IN_U8 ? a.in_index : nullptr;
+    batch.in_index = in_mode_is_u8(IN_MODE) ? a.in_index : nullptr;
     hipLaunchKernelGGL(kern, dim3(grid, count), dim3(wgrad_threads<IN_MODE, C::NBANDS, DY_POOLED>()), C::LDS_BYTES, a.st, batch,
                        a.n);
     int rc = check_launch("conv3x3_wgrad_kernel");
@@ -715,7 +715,7 @@ int dispatch_wgrad_mode(int in_mode, int cin, int cout, int h, int w, const Wgra
 int wgrad_slabs_pooled(const char *who, const void *in, const int32_t *index, int in_mode, const float *g, const uint8_t *argmax,
                        void *workspace, size_t workspace_bytes, int n, int cin, int cout, int h, int w, int *n_slabs, void *stream)
 {
-    if (index && in_mode != IN_U8) return fail(PPO_E_INVALID, "%s: the index applies to uint8 observations", who);
+    if (index && !in_mode_is_u8(in_mode)) return fail(PPO_E_INVALID, "%s: the index applies to uint8 observations", who);
     if (n <= 0) return fail(PPO_E_INVALID, "%s: n must be positive", who);
     if (!in || !g || !argmax || !workspace || !n_slabs) return fail(PPO_E_INVALID, "%s: null pointer", who);
     WgradArgs a;

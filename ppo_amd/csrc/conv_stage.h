@@ -17,7 +17,12 @@
 
 namespace ppo {
 
-enum { IN_NONE = 0, IN_RELU = 1, IN_U8 = 2 };
+enum { IN_NONE = 0, IN_RELU = 1, IN_U8 = 2, IN_U8_CENTERED = 4, IN_U8_UNIT = 5 };
+
+// the three uint8 preparations (--observation_scaling=scaled | centered | unit) read bytes; the other modes read floats
+constexpr bool in_mode_is_u8(int in_mode) { return in_mode == IN_U8 || in_mode == IN_U8_CENTERED || in_mode == IN_U8_UNIT; }
+// centered / unit map byte 0 to -0.5 / -3: a staging path must then keep padding apart from a byte 0
+constexpr bool in_mode_is_signed_u8(int in_mode) { return in_mode == IN_U8_CENTERED || in_mode == IN_U8_UNIT; }
 
 // A run-time in_mode as a template argument: f(std::integral_constant<int, MODE>{}) for the mode of this call, or
 // kNoSuchMode for a value that is no mode.  An entry point that refuses one of the modes returns kNoSuchMode from f for it
@@ -30,6 +35,8 @@ int with_in_mode(int in_mode, F &&f)
         case IN_NONE: return f(std::integral_constant<int, IN_NONE>{});
         case IN_RELU: return f(std::integral_constant<int, IN_RELU>{});
         case IN_U8: return f(std::integral_constant<int, IN_U8>{});
+        case IN_U8_CENTERED: return f(std::integral_constant<int, IN_U8_CENTERED>{});
+        case IN_U8_UNIT: return f(std::integral_constant<int, IN_U8_UNIT>{});
     }
     return kNoSuchMode;
 }
@@ -44,6 +51,42 @@ __device__ __forceinline__ float u8_unit(float x)
     const float q = x * r;
     return fmaf(fmaf(q, -255.0f, x), r, q);
 }
+
+// The signed preparations (rl/models.py:846-855), every operation rounded on its own as torch rounds it:
+//   centered: x / 255 - 0.5        unit: (x / 255 - 0.5) * 6
+// The subtraction is inexact for 63 of the 256 bytes, so neither fma(q, 6, -3), nor x * (6 / 255) - 3, nor one rounding
+// of the exact value gives the reference's bits (tests/test_obs_scaling_cpu.py counts the differences of each).
+// c * 6 as a product of its own: under the compiler's default contraction a consumer's `- m` (the normaliser, the bf16
+// split's x - hi) would otherwise fuse with it into fma(c, 6, -m), which skips the rounding torch applies to the product
+__device__ __forceinline__ float times6_rounded(float c)
+{
+#pragma clang fp contract(off)
+    return c * 6.0f;
+}
+__device__ __forceinline__ float u8_centered(float x) { return __fsub_rn(u8_unit(x), 0.5f); }
+__device__ __forceinline__ float u8_scaled_unit(float x) { return times6_rounded(__fsub_rn(u8_unit(x), 0.5f)); }
+
+// byte value (as a float) -> the network's input under a uint8 IN_MODE
+template <int IN_MODE>
+__device__ __forceinline__ float u8_prep(float x)
+{
+    static_assert(in_mode_is_u8(IN_MODE), "a uint8 mode");
+    if constexpr (IN_MODE == IN_U8_CENTERED) return u8_centered(x);
+    else if constexpr (IN_MODE == IN_U8_UNIT) return u8_scaled_unit(x);
+    else return u8_unit(x);
+}
+// the same for a run-time mode (the generic kernels)
+__device__ __forceinline__ float u8_prep(float x, int in_mode)
+{
+    const float q = u8_unit(x);
+    if (in_mode == IN_U8) return q;
+    const float c = __fsub_rn(q, 0.5f);
+    return in_mode == IN_U8_CENTERED ? c : times6_rounded(c);
+}
+
+// What the raw-byte staging paths put where the image has no pixel (rows outside it, channels >= C) under the signed
+// preparations: no byte has this value, and the store turns it into 0.0f instead of f(0).
+constexpr uint32_t kNoPixel = 0x100u;
 
 // s_dst[c * PLANE + r * PW + col] for c < CP, r < ROWS, col < PW holds
 //   f(src[img][c][y0 + r - HALO][col - HALO])   (0 outside the image or for c >= C)
@@ -79,10 +122,10 @@ __device__ __forceinline__ void stage_band(const void *__restrict__ src_, int im
             const int gy = y0 + r - HALO;
             const int gx = col - HALO;
             off[u] = in_lds ? c * PLANE + r * PW + col : -1;
-            v[u] = 0.f;
+            v[u] = in_mode_is_signed_u8(IN_MODE) ? -1.f : 0.f;  // signed: no byte is negative (padding, see below)
             if (in_lds && c < C && gy >= 0 && gy < H && gx >= 0 && gx < W) {
                 const size_t gi = ((size_t)(img * C + c) * H + gy) * W + gx;
-                if (IN_MODE == IN_U8) v[u] = (float)static_cast<const uint8_t *>(src_)[gi];
+                if (in_mode_is_u8(IN_MODE)) v[u] = (float)static_cast<const uint8_t *>(src_)[gi];
                 else v[u] = static_cast<const float *>(src_)[gi];
             }
         }
@@ -90,7 +133,8 @@ __device__ __forceinline__ void stage_band(const void *__restrict__ src_, int im
         for (int u = 0; u < U; ++u) {
             if (off[u] >= 0) {
                 float x = v[u];
-                if (IN_MODE == IN_U8) x = u8_unit(x);
+                if constexpr (in_mode_is_signed_u8(IN_MODE)) x = x < 0.f ? 0.f : u8_prep<IN_MODE>(x);  // padding stays 0, not f(0)
+                else if constexpr (IN_MODE == IN_U8) x = u8_unit(x);
                 if (IN_MODE == IN_RELU) x = fmaxf(x, 0.f);
                 s_dst[off[u]] = x;
             }
@@ -303,10 +347,10 @@ __device__ __forceinline__ void stage_band_flat(const void *__restrict__ src_, i
             const bool in_lds = q < Q && r < ROWS && col < W;
             const int gy = y0 + r - 1;
             off[u] = in_lds ? c * PLANE + G + r * W + col : -1;
-            v[u] = 0.f;
+            v[u] = in_mode_is_signed_u8(IN_MODE) ? -1.f : 0.f;
             if (in_lds && c < C && gy >= 0 && gy < H) {
                 const size_t gi = ((size_t)(img * C + c) * H + gy) * W + col;
-                if (IN_MODE == IN_U8) v[u] = (float)static_cast<const uint8_t *>(src_)[gi];
+                if (in_mode_is_u8(IN_MODE)) v[u] = (float)static_cast<const uint8_t *>(src_)[gi];
                 else v[u] = static_cast<const float *>(src_)[gi];
             }
         }
@@ -314,7 +358,8 @@ __device__ __forceinline__ void stage_band_flat(const void *__restrict__ src_, i
         for (int u = 0; u < U; ++u) {
             if (off[u] >= 0) {
                 float x = v[u];
-                if (IN_MODE == IN_U8) x = u8_unit(x);
+                if constexpr (in_mode_is_signed_u8(IN_MODE)) x = x < 0.f ? 0.f : u8_prep<IN_MODE>(x);  // padding stays 0, not f(0)
+                else if constexpr (IN_MODE == IN_U8) x = u8_unit(x);
                 if (IN_MODE == IN_RELU) x = fmaxf(x, 0.f);
                 s_dst[off[u]] = x;
             }
@@ -351,10 +396,10 @@ __device__ __forceinline__ void band_flat_load(const void *__restrict__ src_, in
         const int r = (qq % M::RB) * M::RSTEP + rw;
         const int col = col0 + 64 * pass;
         const int gy = y0 + r - 1;
-        raw[q] = 0;
+        raw[q] = in_mode_is_signed_u8(IN_MODE) ? kNoPixel : 0;
         if (r < ROWS && col < W && c < C && gy >= 0 && gy < H) {
             const size_t gi = ((size_t)(img * C + c) * H + gy) * W + col;
-            if (IN_MODE == IN_U8) raw[q] = static_cast<const uint8_t *>(src_)[gi];
+            if (in_mode_is_u8(IN_MODE)) raw[q] = static_cast<const uint8_t *>(src_)[gi];
             else raw[q] = static_cast<const uint32_t *>(src_)[gi];
         }
     }
@@ -377,7 +422,8 @@ __device__ __forceinline__ void band_flat_store(const uint32_t (&raw)[FlatMap<CP
         const int col = col0 + 64 * pass;
         if (r < ROWS && col < W) {
             float x;
-            if (IN_MODE == IN_U8) x = u8_unit((float)raw[q]);
+            if constexpr (in_mode_is_signed_u8(IN_MODE)) x = raw[q] == kNoPixel ? 0.f : u8_prep<IN_MODE>((float)raw[q]);
+            else if constexpr (IN_MODE == IN_U8) x = u8_unit((float)raw[q]);
             else x = __uint_as_float(raw[q]);
             if (IN_MODE == IN_RELU) x = fmaxf(x, 0.f);
             s_dst[c * PLANE + G + r * W + col] = x;
@@ -416,21 +462,29 @@ __device__ __forceinline__ void band_u8x4_load(const void *__restrict__ src_, in
     }
 }
 
-template <int C, int W, int ROWS, int PLANE, int G, int NTHREADS>
+// Under the signed preparations a dword of four zero bytes may be pixels (-> f(0)) or a row outside the image (-> 0.0f), and
+// a dword has no room for a marker: the store is told the band's y0 again and repeats the load's row test (H, y0 are unused
+// by IN_U8, whose f(0) is 0).
+template <int C, int W, int ROWS, int PLANE, int G, int NTHREADS, int IN_MODE = IN_U8, int H = 0>
 __device__ __forceinline__ void band_u8x4_store(const uint32_t (&raw)[FlatU8Map<C, W, ROWS, NTHREADS>::Q],
-                                                float *__restrict__ s_dst, int tid)
+                                                float *__restrict__ s_dst, int tid, int y0 = 0)
 {
     using M = FlatU8Map<C, W, ROWS, NTHREADS>;
     static_assert(PLANE % 4 == 0 && G % 4 == 0, "16-byte aligned LDS stores");
+    static_assert(in_mode_is_u8(IN_MODE) && (IN_MODE == IN_U8 || H > 0), "a uint8 mode; the signed ones need the map's height");
 #pragma unroll
     for (int q = 0; q < M::Q; ++q) {
         const int idx = tid + q * NTHREADS;
         if (idx < C * M::DW) {
             const int c = idx / M::DW, d = idx % M::DW;
             const uint32_t v = raw[q];
-            *reinterpret_cast<float4 *>(s_dst + c * PLANE + G + 4 * d) =
-                make_float4(u8_unit((float)(v & 0xffu)), u8_unit((float)((v >> 8) & 0xffu)),
-                            u8_unit((float)((v >> 16) & 0xffu)), u8_unit((float)(v >> 24)));
+            float4 x = make_float4(u8_prep<IN_MODE>((float)(v & 0xffu)), u8_prep<IN_MODE>((float)((v >> 8) & 0xffu)),
+                                   u8_prep<IN_MODE>((float)((v >> 16) & 0xffu)), u8_prep<IN_MODE>((float)(v >> 24)));
+            if constexpr (in_mode_is_signed_u8(IN_MODE)) {
+                const int gy = y0 + (4 * d) / W - 1;
+                if (gy < 0 || gy >= H) x = make_float4(0.f, 0.f, 0.f, 0.f);
+            }
+            *reinterpret_cast<float4 *>(s_dst + c * PLANE + G + 4 * d) = x;
         }
     }
 }

@@ -18,8 +18,8 @@ using tile::kTK;
 
 __device__ __forceinline__ float load_in(const void *in, int in_mode, long long off)
 {
-    return in_mode == PPO_IN_U8 ? u8_unit((float)static_cast<const uint8_t *>(in)[off])
-                                : static_cast<const float *>(in)[off];
+    return in_mode_is_u8(in_mode) ? u8_prep((float)static_cast<const uint8_t *>(in)[off], in_mode)
+                                  : static_cast<const float *>(in)[off];
 }
 __device__ __forceinline__ float load_gated(const float *dy, const float *gate, long long off)
 {
@@ -172,8 +172,8 @@ int launch_forward(const char *what, Act act, const void *in, int in_mode, const
     csi::Geom g;
     if (int rc = check_geometry(what, n, cin, h, w, cout, kh, kw, stride, &g)) return rc;
     if (in == nullptr || weight == nullptr || out == nullptr) return fail(PPO_E_INVALID, "%s: null pointer", what);
-    if (in_mode != PPO_IN_NONE && in_mode != PPO_IN_U8)
-        return fail(PPO_E_INVALID, "%s: in_mode %d (PPO_IN_NONE | PPO_IN_U8)", what, in_mode);
+    if (in_mode != PPO_IN_NONE && !in_mode_is_u8(in_mode))
+        return fail(PPO_E_INVALID, "%s: in_mode %d (PPO_IN_NONE | PPO_IN_U8 | PPO_IN_U8_CENTERED | PPO_IN_U8_UNIT)", what, in_mode);
     ForwardOp<Act> op{g, act, in, in_mode, weight, bias, out, act_out ? 1 : 0, csi::fwd_m(g), cout, csi::fwd_k(g)};
     Loop::launch(op, gemm_grid(op.M, op.N, 1), as_stream(stream));
     return check_launch(what);
@@ -200,8 +200,8 @@ int launch_backward_weight(const char *what, Act act, const void *in, int in_mod
     if (int rc = check_geometry(what, n, cin, h, w, cout, kh, kw, stride, &g)) return rc;
     if (in == nullptr || dy == nullptr || dweight == nullptr || workspace == nullptr)
         return fail(PPO_E_INVALID, "%s: null pointer", what);
-    if (in_mode != PPO_IN_NONE && in_mode != PPO_IN_U8)
-        return fail(PPO_E_INVALID, "%s: in_mode %d (PPO_IN_NONE | PPO_IN_U8)", what, in_mode);
+    if (in_mode != PPO_IN_NONE && !in_mode_is_u8(in_mode))
+        return fail(PPO_E_INVALID, "%s: in_mode %d (PPO_IN_NONE | PPO_IN_U8 | PPO_IN_U8_CENTERED | PPO_IN_U8_UNIT)", what, in_mode);
     int rows;
     const int slabs = wgrad_slabs(g, &rows);
     const int K = csi::fwd_k(g);

@@ -25,10 +25,22 @@
 namespace ppo {
 namespace {
 
+// A byte under preparation `prep` (PPO_OBS_U8 | PPO_OBS_U8_CENTERED | PPO_OBS_U8_UNIT; rl/models.py:846-855), each operation
+// rounded on its own as torch rounds it.
+__device__ __forceinline__ float prep_u8(uint8_t byte, int prep)
+{
+#pragma clang fp contract(off)  // the product below stays a product: fused with normalise()'s `- m` it would skip a rounding
+    const float q = (float)byte / 255.0f;
+    if (prep == PPO_OBS_U8) return q;
+    const float c = q - 0.5f;
+    return prep == PPO_OBS_U8_CENTERED ? c : c * 6.0f;
+}
 __device__ __forceinline__ float prep(const void *x, size_t i, int is_u8)
 {
-    return is_u8 ? (float)static_cast<const uint8_t *>(x)[i] / 255.0f : static_cast<const float *>(x)[i];
+    return is_u8 ? prep_u8(static_cast<const uint8_t *>(x)[i], is_u8) : static_cast<const float *>(x)[i];
 }
+// is_u8 as the entry points take it: PPO_OBS_F32 .. PPO_OBS_U8_UNIT
+inline bool known_prep(int is_u8) { return is_u8 >= PPO_OBS_F32 && is_u8 <= PPO_OBS_U8_UNIT; }
 
 __global__ __launch_bounds__(256) void obs_moments_kernel(const void *__restrict__ x, int is_u8, int B, int F,
                                                           double *__restrict__ moments)
@@ -79,7 +91,7 @@ __device__ __forceinline__ float normalise(float v, float m, float s, float eps)
 }
 
 // VEC = 4 when F % 4 == 0 (rows then keep 16-byte alignment), else 1.
-template <int VEC, bool U8>
+template <int VEC, int U8>
 __global__ __launch_bounds__(256) void obs_normalize_kernel(const void *__restrict__ x, const float *__restrict__ mu,
                                                             const float *__restrict__ std, float eps,
                                                             float *__restrict__ out, size_t n_vec, int fv)
@@ -90,7 +102,7 @@ __global__ __launch_bounds__(256) void obs_normalize_kernel(const void *__restri
             float4 v;
             if constexpr (U8) {
                 const uchar4 r = static_cast<const uchar4 *>(x)[i];
-                v = make_float4((float)r.x / 255.0f, (float)r.y / 255.0f, (float)r.z / 255.0f, (float)r.w / 255.0f);
+                v = make_float4(prep_u8(r.x, U8), prep_u8(r.y, U8), prep_u8(r.z, U8), prep_u8(r.w, U8));
             } else {
                 v = static_cast<const float4 *>(x)[i];
             }
@@ -105,7 +117,7 @@ __global__ __launch_bounds__(256) void obs_normalize_kernel(const void *__restri
 
 // out[b, p] = normalise(x[row(b), channel, p]), row(b) = index ? index[b] : b;  hw_v = H*W / VEC, plane_v the offset of
 // the channel inside a row and row_v the row length, both in units of VEC elements
-template <int VEC, bool U8>
+template <int VEC, int U8>
 __global__ __launch_bounds__(256) void obs_normalize_channel_kernel(const void *__restrict__ x, const int32_t *__restrict__ index,
                                                                     const float *__restrict__ mu, const float *__restrict__ std,
                                                                     float eps, float *__restrict__ out, size_t n_vec, int hw_v,
@@ -119,7 +131,7 @@ __global__ __launch_bounds__(256) void obs_normalize_channel_kernel(const void *
             float4 v;
             if constexpr (U8) {
                 const uchar4 r = static_cast<const uchar4 *>(x)[src];
-                v = make_float4((float)r.x / 255.0f, (float)r.y / 255.0f, (float)r.z / 255.0f, (float)r.w / 255.0f);
+                v = make_float4(prep_u8(r.x, U8), prep_u8(r.y, U8), prep_u8(r.z, U8), prep_u8(r.w, U8));
             } else {
                 v = static_cast<const float4 *>(x)[src];
             }
@@ -142,7 +154,8 @@ extern "C" int ppo_obs_moments_f64(const void *x, int is_u8, int B, int F, doubl
     using namespace ppo;
     if (B <= 0 || F <= 0) return fail(PPO_E_INVALID, "ppo_obs_moments_f64: bad shape [%d, %d]", B, F);
     if (!x || !moments) return fail(PPO_E_INVALID, "ppo_obs_moments_f64: null pointer");
-    hipLaunchKernelGGL(obs_moments_kernel, dim3((F + 255) / 256), dim3(256), 0, as_stream(stream), x, is_u8 ? 1 : 0, B, F,
+    if (!known_prep(is_u8)) return fail(PPO_E_INVALID, "ppo_obs_moments_f64: is_u8 %d (PPO_OBS_F32 .. PPO_OBS_U8_UNIT)", is_u8);
+    hipLaunchKernelGGL(obs_moments_kernel, dim3((F + 255) / 256), dim3(256), 0, as_stream(stream), x, is_u8, B, F,
                        moments);
     return check_launch("obs_moments_kernel");
 }
@@ -167,22 +180,23 @@ extern "C" int ppo_obs_normalize_f32(const void *x, int is_u8, const float *mu, 
     if (B < 0 || F <= 0) return fail(PPO_E_INVALID, "ppo_obs_normalize_f32: bad shape [%d, %d]", B, F);
     if (B == 0) return PPO_OK;
     if (!x || !mu || !std || !out) return fail(PPO_E_INVALID, "ppo_obs_normalize_f32: null pointer");
+    if (!known_prep(is_u8)) return fail(PPO_E_INVALID, "ppo_obs_normalize_f32: is_u8 %d (PPO_OBS_F32 .. PPO_OBS_U8_UNIT)", is_u8);
     const size_t n = (size_t)B * F;
     const bool vec = F % 4 == 0 && aligned(x, is_u8 ? 4 : 16) && aligned(out, 16) && aligned(mu, 16) && aligned(std, 16);
     hipStream_t st = as_stream(stream);
-    if (vec) {
-        if (is_u8)
-            hipLaunchKernelGGL((obs_normalize_kernel<4, true>), dim3(grid_for(n / 4)), dim3(256), 0, st, x, mu, std, eps, out,
-                               n / 4, F / 4);
-        else
-            hipLaunchKernelGGL((obs_normalize_kernel<4, false>), dim3(grid_for(n / 4)), dim3(256), 0, st, x, mu, std, eps, out,
-                               n / 4, F / 4);
-    } else {
-        if (is_u8)
-            hipLaunchKernelGGL((obs_normalize_kernel<1, true>), dim3(grid_for(n)), dim3(256), 0, st, x, mu, std, eps, out, n, F);
-        else
-            hipLaunchKernelGGL((obs_normalize_kernel<1, false>), dim3(grid_for(n)), dim3(256), 0, st, x, mu, std, eps, out, n, F);
+#define PPO_LAUNCH_NORMALIZE(VEC, U8)                                                                                     \
+    hipLaunchKernelGGL((obs_normalize_kernel<VEC, U8>), dim3(grid_for(n / (VEC))), dim3(256), 0, st, x, mu, std, eps, out, \
+                       n / (VEC), F / (VEC))
+#define PPO_LAUNCH_NORMALIZE_PREP(VEC)                                        \
+    switch (is_u8) {                                                          \
+        case PPO_OBS_F32: PPO_LAUNCH_NORMALIZE(VEC, PPO_OBS_F32); break;      \
+        case PPO_OBS_U8: PPO_LAUNCH_NORMALIZE(VEC, PPO_OBS_U8); break;        \
+        case PPO_OBS_U8_CENTERED: PPO_LAUNCH_NORMALIZE(VEC, PPO_OBS_U8_CENTERED); break; \
+        default: PPO_LAUNCH_NORMALIZE(VEC, PPO_OBS_U8_UNIT); break;           \
     }
+    if (vec) { PPO_LAUNCH_NORMALIZE_PREP(4) } else { PPO_LAUNCH_NORMALIZE_PREP(1) }
+#undef PPO_LAUNCH_NORMALIZE_PREP
+#undef PPO_LAUNCH_NORMALIZE
     return check_launch("obs_normalize_kernel");
 }
 
@@ -194,6 +208,8 @@ extern "C" int ppo_obs_normalize_channel_f32(const void *x, int is_u8, const int
         return fail(PPO_E_INVALID, "ppo_obs_normalize_channel_f32: bad shape [%d, %d, %d, %d] / channel %d", B, C, H, W, channel);
     if (B == 0) return PPO_OK;
     if (!x || !mu || !std || !out) return fail(PPO_E_INVALID, "ppo_obs_normalize_channel_f32: null pointer");
+    if (!known_prep(is_u8))
+        return fail(PPO_E_INVALID, "ppo_obs_normalize_channel_f32: is_u8 %d (PPO_OBS_F32 .. PPO_OBS_U8_UNIT)", is_u8);
     const size_t hw = (size_t)H * W, n = (size_t)B * hw;
     const bool vec = hw % 4 == 0 && aligned(x, is_u8 ? 4 : 16) && aligned(out, 16) && aligned(mu, 16) && aligned(std, 16);
     const size_t v = vec ? 4 : 1;
@@ -201,11 +217,15 @@ extern "C" int ppo_obs_normalize_channel_f32(const void *x, int is_u8, const int
 #define PPO_LAUNCH_CHANNEL(VEC, U8)                                                                                       \
     hipLaunchKernelGGL((obs_normalize_channel_kernel<VEC, U8>), dim3(grid_for(n / v)), dim3(256), 0, st, x, index, mu, std, \
                        eps, out, n / v, (int)(hw / v), (size_t)channel * hw / v, (size_t)C * hw / v)
-    if (vec) {
-        if (is_u8) PPO_LAUNCH_CHANNEL(4, true); else PPO_LAUNCH_CHANNEL(4, false);
-    } else {
-        if (is_u8) PPO_LAUNCH_CHANNEL(1, true); else PPO_LAUNCH_CHANNEL(1, false);
+#define PPO_LAUNCH_CHANNEL_PREP(VEC)                                        \
+    switch (is_u8) {                                                        \
+        case PPO_OBS_F32: PPO_LAUNCH_CHANNEL(VEC, PPO_OBS_F32); break;      \
+        case PPO_OBS_U8: PPO_LAUNCH_CHANNEL(VEC, PPO_OBS_U8); break;        \
+        case PPO_OBS_U8_CENTERED: PPO_LAUNCH_CHANNEL(VEC, PPO_OBS_U8_CENTERED); break; \
+        default: PPO_LAUNCH_CHANNEL(VEC, PPO_OBS_U8_UNIT); break;           \
     }
+    if (vec) { PPO_LAUNCH_CHANNEL_PREP(4) } else { PPO_LAUNCH_CHANNEL_PREP(1) }
+#undef PPO_LAUNCH_CHANNEL_PREP
 #undef PPO_LAUNCH_CHANNEL
     return check_launch("obs_normalize_channel_kernel");
 }

@@ -40,6 +40,29 @@ __device__ __forceinline__ float normalise(float v, float m, float s, float eps)
     return fminf(fmaxf((v - m) / (s + eps), -5.0f), 5.0f);  // csrc/obs_norm.hip: IEEE subtract / add / divide
 }
 
+// the normed modes come in three preparations of the byte (--observation_scaling): o/255, o/255 - 0.5, (o/255 - 0.5) * 6
+constexpr bool hash_mode_normed(int mode)
+{
+    return mode == PPO_HASH_NORMED || mode == PPO_HASH_NORMED_OFFSET || (mode >= PPO_HASH_NORMED_CENTERED && mode <= PPO_HASH_NORMED_OFFSET_UNIT);
+}
+constexpr bool hash_mode_known(int mode) { return (mode >= PPO_HASH_RAW && mode <= PPO_HASH_NORMED_OFFSET) || hash_mode_normed(mode); }
+constexpr bool hash_mode_offset(int mode)
+{
+    return mode == PPO_HASH_NORMED_OFFSET || mode == PPO_HASH_NORMED_OFFSET_CENTERED || mode == PPO_HASH_NORMED_OFFSET_UNIT;
+}
+
+// prep_for_model (rl/models.py:846-855) of one byte, each operation rounded on its own (no contraction: fused with
+// normalise()'s `- m` the product would skip a rounding)
+template <int MODE>
+__device__ __forceinline__ float prepared(unsigned o)
+{
+#pragma clang fp contract(off)
+    float p = (float)o / 255.0f;
+    if constexpr (MODE >= PPO_HASH_NORMED_CENTERED) p = p - 0.5f;
+    if constexpr (MODE >= PPO_HASH_NORMED_UNIT) p = p * 6.0f;
+    return p;
+}
+
 // one element of the hash input from one observation byte (rl/rollout.py:670-684)
 template <int MODE>
 __device__ __forceinline__ float hash_input(unsigned o, unsigned q, float m, float s, float eps)
@@ -47,8 +70,8 @@ __device__ __forceinline__ float hash_input(unsigned o, unsigned q, float m, flo
     if (q > 1u) o = (o / q) * q;
     if constexpr (MODE == PPO_HASH_RAW) return (float)o;
     if constexpr (MODE == PPO_HASH_RAW_CENTERED) return (float)o - 128.0f;
-    const float v = normalise((float)o / 255.0f, m, s, eps);
-    if constexpr (MODE == PPO_HASH_NORMED) return v;
+    const float v = normalise(prepared<MODE>(o), m, s, eps);
+    if constexpr (!hash_mode_offset(MODE)) return v;
     return v + 3.0f;
 }
 
@@ -61,7 +84,7 @@ __global__ __launch_bounds__(kHashThreads) void state_hash_kernel(const uint8_t 
                                                                   const float *__restrict__ w, const float *__restrict__ bias,
                                                                   int bits, int32_t *__restrict__ out)
 {
-    constexpr bool kNormed = MODE == PPO_HASH_NORMED || MODE == PPO_HASH_NORMED_OFFSET;
+    constexpr bool kNormed = hash_mode_normed(MODE);
     __shared__ double s_part[kHashWaves][NB];
     const uint8_t *row = obs + (size_t)blockIdx.x * row_stride;
     double acc[NB];
@@ -237,7 +260,11 @@ void launch_hash_mode(int mode, Args... a)
     case PPO_HASH_RAW: launch_hash<NB, PPO_HASH_RAW>(a...); break;
     case PPO_HASH_RAW_CENTERED: launch_hash<NB, PPO_HASH_RAW_CENTERED>(a...); break;
     case PPO_HASH_NORMED: launch_hash<NB, PPO_HASH_NORMED>(a...); break;
-    default: launch_hash<NB, PPO_HASH_NORMED_OFFSET>(a...); break;
+    case PPO_HASH_NORMED_OFFSET: launch_hash<NB, PPO_HASH_NORMED_OFFSET>(a...); break;
+    case PPO_HASH_NORMED_CENTERED: launch_hash<NB, PPO_HASH_NORMED_CENTERED>(a...); break;
+    case PPO_HASH_NORMED_OFFSET_CENTERED: launch_hash<NB, PPO_HASH_NORMED_OFFSET_CENTERED>(a...); break;
+    case PPO_HASH_NORMED_UNIT: launch_hash<NB, PPO_HASH_NORMED_UNIT>(a...); break;
+    default: launch_hash<NB, PPO_HASH_NORMED_OFFSET_UNIT>(a...); break;
     }
 }
 
@@ -255,8 +282,8 @@ extern "C" int ppo_state_hash_i32(const uint8_t *obs, int B, int C, int H, int W
         return fail(PPO_E_INVALID, "ppo_state_hash_i32: planes %d is neither 1 nor C = %d", planes, C);
     if (bits < 1 || bits > kMaxBits) return fail(PPO_E_INVALID, "ppo_state_hash_i32: bits %d outside [1, %d]", bits, kMaxBits);
     if (quantize < 0 || quantize > 255) return fail(PPO_E_INVALID, "ppo_state_hash_i32: quantize %d outside [0, 255]", quantize);
-    if (mode < PPO_HASH_RAW || mode > PPO_HASH_NORMED_OFFSET) return fail(PPO_E_INVALID, "ppo_state_hash_i32: bad mode %d", mode);
-    const bool normed = mode == PPO_HASH_NORMED || mode == PPO_HASH_NORMED_OFFSET;
+    if (!hash_mode_known(mode)) return fail(PPO_E_INVALID, "ppo_state_hash_i32: bad mode %d", mode);
+    const bool normed = hash_mode_normed(mode);
     if (!obs || !weight || !bias || !out || (normed && (!mu || !std)))
         return fail(PPO_E_INVALID, "ppo_state_hash_i32: null pointer");
     if (B == 0) return PPO_OK;

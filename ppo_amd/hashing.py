@@ -24,6 +24,12 @@ WEIGHT_RANGE = 0.01      # rl/hash.py:35
 MAX_BITS = 24
 INPUT_MODES = {"raw": _lib.PPO_HASH_RAW, "raw_centered": _lib.PPO_HASH_RAW_CENTERED, "normed": _lib.PPO_HASH_NORMED,
                "normed_offset": _lib.PPO_HASH_NORMED_OFFSET}
+# the normed inputs under the signed --observation_scaling values: the normaliser saw prep_for_model's output
+# (rl/rollout.py:679-684), so the hash input is formed from the same preparation of the byte
+NORMED_MODES = {("normed", "scaled"): _lib.PPO_HASH_NORMED, ("normed_offset", "scaled"): _lib.PPO_HASH_NORMED_OFFSET,
+                ("normed", "centered"): _lib.PPO_HASH_NORMED_CENTERED,
+                ("normed_offset", "centered"): _lib.PPO_HASH_NORMED_OFFSET_CENTERED,
+                ("normed", "unit"): _lib.PPO_HASH_NORMED_UNIT, ("normed_offset", "unit"): _lib.PPO_HASH_NORMED_OFFSET_UNIT}
 BONUS_METHODS = {"hyperbolic": _lib.PPO_HASH_BONUS_HYPERBOLIC, "quadratic": _lib.PPO_HASH_BONUS_QUADRATIC,
                  "binary": _lib.PPO_HASH_BONUS_BINARY}
 
@@ -79,7 +85,8 @@ class LinearStateHasher:
                           norm=None):
         """Hashes of uint8 observations [B, C, H, W] on the device (a row slice of a larger buffer is fine), written to
         `out` (int32 [B], contiguous; default: a fresh tensor).  With input_space[0] == 1 < C the first plane alone is read.
-        `norm`: the model's ObsNormalizer, whose current float32 constants the normed modes use.  No host read."""
+        `norm`: the model's ObsNormalizer, whose current float32 constants and observation_scaling the normed modes use.
+        No host read."""
         if obs.dtype != torch.uint8 or obs.dim() != 4 or not obs.is_contiguous() or obs.device != self.weight.device:
             raise ValueError(f"expected a contiguous uint8 [B, C, H, W] tensor on {self.weight.device}")
         B, C, H, W = (int(d) for d in obs.shape)
@@ -93,7 +100,8 @@ class LinearStateHasher:
             out = torch.empty(B, dtype=torch.int32, device=obs.device)
         elif out.dtype != torch.int32 or out.numel() != B or not out.is_contiguous():
             raise ValueError("out must be a contiguous int32 tensor with one entry per row")
-        _call(self.lib, "ppo_state_hash_i32", _p(obs), B, C, H, W, planes, int(quantize), INPUT_MODES[mode],
+        code = NORMED_MODES[mode, getattr(norm, "observation_scaling", "scaled")] if normed else INPUT_MODES[mode]
+        _call(self.lib, "ppo_state_hash_i32", _p(obs), B, C, H, W, planes, int(quantize), code,
               _p(norm.mu) if normed else None, _p(norm.std) if normed else None, float(norm.norm_eps) if normed else 0.0,
               _p(self.weight), _p(self.bias), self.bits, _p(out))
         return out

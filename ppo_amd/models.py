@@ -26,6 +26,19 @@ from . import _lib
 from .rnd import RNDNets, init_rnd_parameters  # noqa: F401  (init_rnd_parameters: the RND half of init_parameters)
 
 IN_NONE, IN_RELU, IN_U8 = _lib.PPO_IN_NONE, _lib.PPO_IN_RELU, _lib.PPO_IN_U8
+# --observation_scaling (rl/models.py:846-855): how a uint8 observation becomes the network's input.  Per value, the
+# in_mode of the convolution launches that read the bytes and the `is_u8` code of the ppo_obs_* launches.  Float32
+# observations are used as they are whatever the value, as in the reference.
+OBSERVATION_SCALINGS = {"scaled": (_lib.PPO_IN_U8, _lib.PPO_OBS_U8), "centered": (_lib.PPO_IN_U8_CENTERED, _lib.PPO_OBS_U8_CENTERED),
+                        "unit": (_lib.PPO_IN_U8_UNIT, _lib.PPO_OBS_U8_UNIT)}
+U8_MODES = frozenset(m for m, _ in OBSERVATION_SCALINGS.values())
+
+
+def check_observation_scaling(observation_scaling):
+    """The reference's refusal (rl/models.py:855)."""
+    if observation_scaling not in OBSERVATION_SCALINGS:
+        raise ValueError(f"Invalid observation_scaling mode {observation_scaling}")
+    return observation_scaling
 _ALIGN = 4  # floats: every parameter starts on a 16-byte boundary
 # bit i set: stack i runs its first convolution fused with the max-pool (bit-identical either way; the choice is
 # a measured one, see DESIGN.md §4)
@@ -426,7 +439,11 @@ class ObsNormalizer:
     `_mu` / `_std`.  One instance is shared by the policy and value nets of a TVFModel; each net applies it in
     `encode`.  Data-parallel ranks all-reduce the batch moments, so every rank holds the same statistics."""
 
-    def __init__(self, input_dims, device, norm_eps: float = 1e-5, frozen: bool = False, epsilon: float = 1e-4):
+    def __init__(self, input_dims, device, norm_eps: float = 1e-5, frozen: bool = False, epsilon: float = 1e-4,
+                 observation_scaling: str = "scaled"):
+        # what a uint8 batch is before it is normalised: prep_for_model's output (rl/models.py:846-855)
+        self.observation_scaling = check_observation_scaling(observation_scaling)
+        self.u8_prep = OBSERVATION_SCALINGS[observation_scaling][1]
         self.input_dims = tuple(int(d) for d in input_dims)
         self.F = int(np.prod(self.input_dims))
         self.device = torch.device(device)
@@ -456,7 +473,7 @@ class ObsNormalizer:
             return
         self._check(x)
         from . import parallel
-        self._call("ppo_obs_moments_f64", _p(x), 1 if x.dtype == torch.uint8 else 0, x.shape[0], self.F,
+        self._call("ppo_obs_moments_f64", _p(x), self.u8_prep if x.dtype == torch.uint8 else 0, x.shape[0], self.F,
                    _p(self._moments))
         n = x.shape[0]
         if parallel.world_size() > 1:
@@ -468,7 +485,7 @@ class ObsNormalizer:
 
     def apply(self, x: torch.Tensor, out: torch.Tensor):
         self._check(x)
-        self._call("ppo_obs_normalize_f32", _p(x), 1 if x.dtype == torch.uint8 else 0, _p(self.mu), _p(self.std),
+        self._call("ppo_obs_normalize_f32", _p(x), self.u8_prep if x.dtype == torch.uint8 else 0, _p(self.mu), _p(self.std),
                    self.norm_eps, _p(out), x.shape[0], self.F)
         return out
 
@@ -496,13 +513,19 @@ class DualHeadNet:
     whatever `precision`) and ``mlp`` (flat float observations);
     encoder activation ``relu`` (fused into the head GEMM's operand load) or ``tanh``.  All heads are ONE
     [nh, hidden] matrix so a forward is one GEMM: columns [policy nA | value VH | advantage nA | tvf K*VH].
+    ``observation_scaling`` (scaled | centered | unit, rl/models.py:846-855) picks the input mode of every launch that
+    reads uint8 observations (`u8_mode`); the launches themselves - fused, indexed, split - are the same in all three.
     """
 
     def __init__(self, encoder: str, input_dims, n_actions: int, hidden_units: int = 256,
                  activation_fn: str = "relu", tvf_fixed_head_horizons=None, tvf_feature_sparsity: float = 0.0,
                  tvf_feature_window: int = -1, head_scale: float = 1.0, value_head_names=("ext",),
-                 head_bias: bool = False, device="cuda", precision: str = "high", **encoder_args):
+                 head_bias: bool = False, device="cuda", precision: str = "high", observation_scaling: str = "scaled",
+                 **encoder_args):
         encoder = encoder.lower()
+        # the in_mode of every launch that reads uint8 observations (float32 ones are read with IN_NONE whatever it says)
+        self.observation_scaling = check_observation_scaling(observation_scaling)
+        self.u8_mode = OBSERVATION_SCALINGS[observation_scaling][0]
         if precision not in ("low", "medium", "high"):
             raise ValueError(f"Invalid precision mode {precision}")
         if encoder not in ("impala", "mlp", "nature", "rtg"):
@@ -804,7 +827,7 @@ class DualHeadNet:
                     self.generic_convs.append(f"encoder.stacks.{si}.firstconv")
                     if not lib.ppo_conv3x3s2_any_supported(cin, cout, h, w):
                         raise _lib.PpoAmdError(f"no 3x3 stride-2 convolution kernel for {cin}->{cout} on {h}x{w}")
-                elif not specialised((IN_U8, IN_NONE) if si == 0 else (IN_NONE,), cin, cout, h, w, si > 0):
+                elif not specialised((self.u8_mode, IN_NONE) if si == 0 else (IN_NONE,), cin, cout, h, w, si > 0):
                     self.generic_convs.append(f"encoder.stacks.{si}.firstconv")
                     if not lib.ppo_conv3x3_any_supported(cin, cout, h, w):
                         raise _lib.PpoAmdError(f"no 3x3 convolution kernel for {cin}->{cout} on {h}x{w}")
@@ -1042,7 +1065,7 @@ class DualHeadNet:
                 # clamp((x - mu) / (std + eps), -5, 5) ahead of the network (rl/models.py:783-784); the net then
                 # sees a float32 input, which is also what its backward reads
                 x_in = self._buf(tag + "xn", tuple(x.shape))
-                self._call("ppo_obs_normalize_f32", _p(x), 1 if x.dtype == torch.uint8 else 0, _p(self.obs_norm.mu),
+                self._call("ppo_obs_normalize_f32", _p(x), self.obs_norm.u8_prep if x.dtype == torch.uint8 else 0, _p(self.obs_norm.mu),
                            _p(self.obs_norm.std), self.obs_norm.norm_eps, _p(x_in), x.shape[0], self.obs_norm.F)
             acts = (self._encode_mlp(x_in, train, tag) if self.encoder_kind == "mlp"
                     else self._encode_nature(x_in, train, tag, tail) if self.encoder_kind == "nature"
@@ -1096,7 +1119,7 @@ class DualHeadNet:
         IMPALA encoder."""
         sp, B = self.spec, x.shape[0]
         acts = {"x": x}
-        cur, mode = x, (IN_U8 if x.dtype == torch.uint8 else IN_NONE)
+        cur, mode = x, (self.u8_mode if x.dtype == torch.uint8 else IN_NONE)
         for name, cin, cout, k, s, h, w, ho, wo in sp.layers:
             y = self._buf(f"{tag}{name}", (B, cout, ho, wo))
             self._call(self._nature_conv(name, "forward"), _p(cur), mode, _p(self.params[f"encoder.{name}.weight"]),
@@ -1113,7 +1136,7 @@ class DualHeadNet:
         action step or the PPO loss) as behind the nature encoder.  Seven launches."""
         sp, B = self.spec, x.shape[0]
         acts = {"x": x}
-        cur, mode = x, (IN_U8 if x.dtype == torch.uint8 else IN_NONE)
+        cur, mode = x, (self.u8_mode if x.dtype == torch.uint8 else IN_NONE)
         for name, cin, cout, k, s, p, h, w, hc, wc, hp, wp in sp.layers:
             y = self._buf(f"{tag}{name}", (B, cout, hc, wc))
             wt, bias = self.params[f"encoder.{name}.weight"], self.params[f"encoder.{name}.bias"]
@@ -1152,7 +1175,7 @@ class DualHeadNet:
         batch-norm launch, convolution with the skip as residual.  No whole-stack, block-fused or split-bf16 launch."""
         sp, B = self.spec, x.shape[0]
         acts = {"x": x}
-        cur, cur_mode = x, (IN_U8 if x.dtype == torch.uint8 else IN_NONE)
+        cur, cur_mode = x, (self.u8_mode if x.dtype == torch.uint8 else IN_NONE)
         for si, (cin, cout, h, w, ho, wo) in enumerate(sp.stacks):
             wname = f"encoder.stacks.{si}.firstconv"
             p = self._buf(f"{tag}p{si}", (B, cout, ho, wo))
@@ -1292,7 +1315,7 @@ class DualHeadNet:
         sp = self.spec
         B = x.shape[0] if index is None else int(index.shape[0])
         acts = {"x": x, "in0_index": index}
-        cur, cur_mode = x, (IN_U8 if x.dtype == torch.uint8 else IN_NONE)
+        cur, cur_mode = x, (self.u8_mode if x.dtype == torch.uint8 else IN_NONE)
         pending = None  # (pooled map, pointer arrays, output buffers) of a stack whose blocks the next launch runs
         pool = sp.down_sample == "pool"
         for si, (cin, cout, h, w, ho, wo) in enumerate(sp.stacks):
@@ -1342,7 +1365,7 @@ class DualHeadNet:
                                _p(self.params[wname + ".bias"]), None, _p(p), B, cin, cout, h, w)
                 else:
                     self._conv(cur, cur_mode, wname, p, None, B, cin, cout, h, w)
-            elif self.split_bf16 and (wname, 0) in self._pk16 and cur_mode != IN_U8 and cur.dtype == torch.float32:
+            elif self.split_bf16 and (wname, 0) in self._pk16 and cur_mode not in U8_MODES and cur.dtype == torch.float32:
                 # --precision=low|medium: the stack-first convolution as split-bf16 products, with the max-pool inside the
                 # launch or behind it
                 if self.lib.ppo_conv3x3_pool_bf16x3_supported(cin, cout, h, w):
@@ -1566,7 +1589,7 @@ class DualHeadNet:
         for li in (2, 1, 0):
             name, cin, cout, k, s, h, w, _ho, _wo = sp.layers[li]
             src = acts[sp.layers[li - 1][0]] if li else x
-            mode = IN_U8 if src.dtype == torch.uint8 else IN_NONE
+            mode = self.u8_mode if src.dtype == torch.uint8 else IN_NONE
             geom = (B, cin, h, w, cout, k, k, s)
             nbytes = int(self.lib.ppo_conv2d_strided_wgrad_workspace_bytes(*geom))
             ws = self._ws("nwgrad_ws_" + name, nbytes)
@@ -1593,7 +1616,7 @@ class DualHeadNet:
         for li in (2, 1, 0):
             name, cin, cout, k, s, p, h, w, hc, wc, _hp, _wp = sp.layers[li]
             src = acts[sp.layers[li - 1][0]] if li else x
-            mode = IN_U8 if src.dtype == torch.uint8 else IN_NONE
+            mode = self.u8_mode if src.dtype == torch.uint8 else IN_NONE
             dy = self._buf("rg_" + name, (B, cout, hc, wc))
             self._call("ppo_maxpool2x2_relu_backward_f32", _p(g), _p(acts[name + "_gate"]), _p(dy), B, cout, hc, wc)
             dw, db = self.grads[f"encoder.{name}.weight"], self.grads[f"encoder.{name}.bias"]
@@ -1672,7 +1695,7 @@ class DualHeadNet:
                 bn_backward(dz0, q_in, g, base + ".bn0", gn, cout, ho, wo)
                 g = gn
             x_in = acts[f"in{si}"]
-            mode = IN_NONE if si > 0 else (IN_U8 if x_in.dtype == torch.uint8 else IN_NONE)
+            mode = IN_NONE if si > 0 else (self.u8_mode if x_in.dtype == torch.uint8 else IN_NONE)
             g_prev = self._buf(f"g{si - 1}_top", (B, cin, hh, ww)) if si > 0 else None
             if sp.down_sample == "stride":
                 nbytes = int(lib.ppo_conv3x3s2_any_wgrad_workspace_bytes(B, cin, cout, hh, ww))
@@ -1877,7 +1900,7 @@ class DualHeadNet:
                 wgrad_blocks(problems, B, cout, ho, wo)
             # max-pool backward, then the stack's first convolution
             x_in = acts[f"in{si}"]
-            mode = IN_NONE if si > 0 else (IN_U8 if x_in.dtype == torch.uint8 else IN_NONE)
+            mode = IN_NONE if si > 0 else (self.u8_mode if x_in.dtype == torch.uint8 else IN_NONE)
             if sp.down_sample != "pool":
                 # no max-pool: g is the gradient of the first convolution's output
                 g_prev = self._buf(f"g{si - 1}_top", (B, cin, hh, ww)) if si > 0 else None
@@ -2353,8 +2376,7 @@ class TVFModel:
                 raise NotImplementedError("RND together with TVF heads is not built (the reference trains TVF on 'ext' only)")
         if dtype != torch.float32:
             raise ValueError("the reference path is float32 (rl/models.py:31-32)")
-        if observation_scaling != "scaled":
-            raise NotImplementedError("observation_scaling='scaled' only (x/255 fused into the first conv)")
+        self.observation_scaling = check_observation_scaling(observation_scaling)
         if isinstance(encoder_args, str):
             import ast
             encoder_args = ast.literal_eval(encoder_args)
@@ -2375,7 +2397,8 @@ class TVFModel:
                                activation_fn=encoder_activation_fn, tvf_fixed_head_horizons=tvf_fixed_head_horizons,
                                tvf_feature_sparsity=tvf_feature_sparsity, tvf_feature_window=tvf_feature_window,
                                head_scale=head_scale, value_head_names=value_head_names, head_bias=head_bias,
-                               device=device, precision=precision, **(encoder_args or {}))
+                               device=device, precision=precision, observation_scaling=observation_scaling,
+                               **(encoder_args or {}))
 
         self.policy_net = make_net()
         self.value_net = make_net() if architecture == "dual" else self.policy_net
@@ -2384,7 +2407,7 @@ class TVFModel:
         self.obs_norm = None
         if self.observation_normalization:
             self.obs_norm = ObsNormalizer(self.input_dims, self.device, norm_eps=norm_eps,
-                                          frozen=freeze_observation_normalization)
+                                          frozen=freeze_observation_normalization, observation_scaling=observation_scaling)
             self.policy_net.obs_norm = self.value_net.obs_norm = self.obs_norm
         self.use_rnd = bool(use_rnd)
         self.rnd = None
@@ -2411,8 +2434,9 @@ class TVFModel:
         return n if self.architecture == "single" else n + self.value_net.n_parameters()
 
     def prep_for_model(self, x):
-        """rl/models.py:824-856: accept ndarray or tensor, uint8 or float; the /255 scaling itself is fused
-        into the first convolution's load."""
+        """rl/models.py:824-856: accept ndarray or tensor, uint8 or float; the scaling itself (`observation_scaling`:
+        x/255, x/255 - 0.5 or (x/255 - 0.5) * 6) is fused into the load of the kernels that read the bytes - the first
+        convolution, the normaliser, the RND input, the hash input.  Float input is used as it is."""
         if isinstance(x, np.ndarray):
             x = torch.from_numpy(x)
         if x.dtype not in (torch.uint8, torch.float32):

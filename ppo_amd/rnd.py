@@ -158,7 +158,7 @@ class RNDNets:
     # ------------------------------------------------------------------ forward
     def normalised_channel(self, x, index: Optional[torch.Tensor], B, tag):
         """clamp((prep(x)[row, -1] - mu) / (std + eps), -5, 5) as [B, 1, H, W] (rl/models.py:719-723), row b of the result
-        read at x[index[b]] when an index is given."""
+        read at x[index[b]] when an index is given.  prep: the normaliser's --observation_scaling for uint8 input."""
         C, H, W = self.input_dims
         if tuple(x.shape[1:]) != self.input_dims or x.dtype not in (torch.uint8, torch.float32) or not x.is_contiguous() \
                 or x.device != self.obs_norm.device:
@@ -167,7 +167,7 @@ class RNDNets:
             raise ValueError("index must be a contiguous int32 tensor with one entry per row")
         n = self.obs_norm
         out = self._buf(tag + "xn", (B, 1, H, W))
-        self._call("ppo_obs_normalize_channel_f32", _p(x), 1 if x.dtype == torch.uint8 else 0, _p(index), _p(n.mu), _p(n.std),
+        self._call("ppo_obs_normalize_channel_f32", _p(x), n.u8_prep if x.dtype == torch.uint8 else 0, _p(index), _p(n.mu), _p(n.std),
                    n.norm_eps, _p(out), B, C, H, W, C - 1)
         return out
 

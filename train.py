@@ -42,6 +42,7 @@ def make_model(log):
         observation_normalization=args.observation_normalization,
         freeze_observation_normalization=args.freeze_observation_normalization,
         norm_eps=args.observation_normalization_epsilon,
+        observation_scaling=args.observation_scaling,
         # train.py:166-178: low / medium let the GPU use reduced-precision convolution arithmetic (there TF32, here the
         # split-bf16 launches of the 32-channel stacks); high is exact float32 everywhere
         precision=args.precision)
