@@ -666,6 +666,18 @@ int ppo_adam_step_scatter_f32(float *params, const float *grads, float *exp_avg,
                               double lr, double beta1, double beta2, double eps, float max_grad_norm, float grad_div,
                               void *workspace, float *grad_norm_out, const int32_t *scatter, int64_t n_scatter,
                               float *packed, void *stream);
+/* The same clip followed by torch.optim.SGD's update without momentum, weight decay or dampening (--*_opt_optimizer=sgd,
+ * rl/rollout.py:137-138, :1287-1321): norm = sqrt(sum g^2) / grad_div, clip = max_grad_norm > 0 ? min(1, max_grad_norm /
+ * (norm + 1e-6)) : 1, w <- w - (float)lr * g * (clip / grad_div), the factor (float)lr * clip / grad_div formed once in
+ * double from the float32 norm and rounded once, then one fused multiply-add per parameter.  The sum-of-squares launch, its grid and its partials
+ * are those of ppo_adam_step_f32, so grad_norm_out (nullable, device) holds the same bits as Adam's for the same grads,
+ * max_grad_norm and grad_div.  workspace: ppo_adam_workspace_bytes() bytes, as for Adam.  n == 0 is a no-op. */
+int ppo_sgd_step_f32(float *params, const float *grads, int64_t n, double lr, float max_grad_norm, float grad_div,
+                     void *workspace, float *grad_norm_out, void *stream);
+/* The SGD step when the per-workgroup partial sums of g^2 already exist (ppo_mlp_train_f32): only the SGD launch, which
+ * re-reduces `partials[0 .. n_partials)` (1 .. 256) in the order the Adam launch does (rl/rollout.py:137-138, :1287-1321). */
+int ppo_sgd_step_presummed_f32(float *params, const float *grads, int64_t n, double lr, float max_grad_norm, float grad_div,
+                               const float *partials, int n_partials, float *grad_norm_out, void *stream);
 
 /*
  * dst[r, :] = src[index[r], :] for r < n_rows; rows are row_bytes bytes (minibatch gather of

@@ -11,6 +11,7 @@ enables them (`--gkl_enabled[=True]`, `--side_enabled[=True]`): every other line
 hashing, the replay buffer, the simple noise scale, the global KL penalty and state-independent exploration were built.
 """
 import argparse
+import os
 import sys
 
 
@@ -58,7 +59,7 @@ class OptimizerConfig(_Group):  # rl/config.py:249-311
         parser.set_defaults(**{f"{self._prefix}_epochs": self.EPOCH_DEFAULTS.get(self._prefix, 0)})
 
     FIELDS = (
-        ("optimizer", str, "adam", "[adam]"),
+        ("optimizer", str, "adam", "[adam|sgd]"),
         ("epochs", int, 2, "training epochs per batch (default: policy 2, value 1, distil 2)"),
         ("mini_batch_size", int, 256, "examples per optimisation step (global, across ranks)"),
         ("lr", float, 2.5e-4, "learning rate"),
@@ -527,6 +528,19 @@ class Config:
             raise ValueError("Invalid clip_mode.")
         if self.tvf.gamma is None:
             self.tvf.gamma = self.gamma
+        # make_optimizer's refusal (rl/rollout.py:126-141), at set-up rather than at the first step, and OptimizerConfig.auto
+        # (rl/config.py:308-311).  The rollout is what one phase sees over all ranks - the quantity the global minibatch
+        # divides: --agents is per rank, so n_steps x agents x world size
+        rollout = self.batch_size * int(os.environ.get("WORLD_SIZE", "1"))
+        for opt in (self.policy_opt, self.value_opt, self.distil_opt, self.rnd_opt):
+            if opt.optimizer not in ("adam", "sgd"):
+                raise ValueError(f"Invalid Optimizer {opt.optimizer}")
+            if opt.adam_beta1 < 0:
+                if opt.epochs == 0 or opt.mini_batch_size <= 0:
+                    raise ValueError(f"--{opt._prefix}_adam_beta1={opt.adam_beta1} (auto) needs --{opt._prefix}_epochs > 0 "
+                                     f"and a positive minibatch: beta1 = 1 - 1 / ((rollout / mini_batch_size) * epochs)")
+                opt.adam_beta1 = 1 - (1 / ((rollout / opt.mini_batch_size) * opt.epochs))
+                print(f"Set {opt._prefix} beta1 to {opt.adam_beta1}")
         # the reference raises these two in the middle of an update (rl/rollout.py:1414, 2096; :1383 for the value loss)
         if self.distil.loss not in DistilConfig.LOSSES:
             raise ValueError(f"Invalid distil_loss {self.distil.loss}")

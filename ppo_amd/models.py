@@ -433,6 +433,37 @@ class AdamState:
             self.exp_avg_sq = torch.zeros_like(flat)
 
 
+def sgd_state_dict(n_parameters: int, lr: float):
+    """`torch.optim.SGD(params, lr=lr).state_dict()` of n_parameters parameters (rl/rollout.py:137-138, :412-421): an
+    empty `state` and one param group with the installed torch's own keys and defaults, taken from a throw-away optimiser
+    on the CPU so that the layout follows torch and not a list written here."""
+    params = [torch.zeros(1, requires_grad=True) for _ in range(int(n_parameters))]
+    return torch.optim.SGD(params, lr=float(lr)).state_dict()
+
+
+def optimizer_layout_kind(sd):
+    """'adam', 'sgd' or None (cannot tell) for an optimiser state dict: torch's Adam groups carry `betas`, its SGD groups
+    `momentum`; the layouts earlier versions of this package wrote (whole `flat` moments; name-keyed moments without
+    param groups) are Adam's."""
+    groups = sd.get("param_groups") or []
+    if "flat" in sd or any("betas" in g for g in groups):
+        return "adam"
+    if any("momentum" in g for g in groups):
+        return "sgd"
+    if any(isinstance(st, dict) and "exp_avg" in st for st in (sd.get("state") or {}).values()):
+        return "adam"
+    return None
+
+
+def check_optimizer_layout(sd, kind):
+    """Refuse a state dict of the other optimiser kind.  Stricter than torch, on purpose: torch.optim.SGD would load an
+    Adam dict (and the reverse) and carry on with the wrong hyper-parameters."""
+    found = optimizer_layout_kind(sd)
+    if found is not None and found != kind:
+        raise ValueError(f"optimizer state dict has the {found} layout but this optimizer is {kind}: the checkpoint was "
+                         f"written with --*_opt_optimizer={found}")
+
+
 class ObsNormalizer:
     """Device-resident form of the reference's observation normaliser (rl/models.py:615-617, 661-694):
     `obs_rms` (utils.RunningMeanStd: float64 mean / var per feature, scalar count) plus the float32 constants
@@ -2292,11 +2323,30 @@ class DualHeadNet:
             self._call("ppo_adam_step_f32", *args, _p(grad_norm_out))
         self.mask_feature_weights()
 
+    def sgd_step(self, lr=2.5e-4, max_grad_norm=20.0, grad_div=1.0, grad_norm_out: Optional[torch.Tensor] = None):
+        """clip_grad_norm_ + torch.optim.SGD.step (no momentum, weight decay or dampening) over the flat buffer
+        (rl/rollout.py:137-138, :1287-1321).  Everything adam_step does around its launch, without moments or a step
+        count.  There is no scatter form: under PPO_AMD_ADAM_SCATTER too the weights are marked changed and the ordinary
+        re-pack follows before the next forward."""
+        ws = self._ws("adam_ws", self.lib.ppo_adam_workspace_bytes())
+        self.mark_weights_changed()
+        n_part, self._presummed = self._presummed, 0
+        args = (_p(self.flat), _p(self.grad), self.flat.numel(), float(lr), float(max_grad_norm), float(grad_div))
+        if n_part and grad_div == 1.0:
+            # the launch that wrote the gradients left the per-workgroup sums of g^2 in the workspace (fused MLP path)
+            self._call("ppo_sgd_step_presummed_f32", *args, _p(ws), n_part, _p(grad_norm_out))
+        else:
+            self._call("ppo_sgd_step_f32", *args, _p(ws), _p(grad_norm_out))
+        self.mask_feature_weights()
+
     # ------------------------------------------------------------------ optimiser state (checkpoints)
     def parameter_order(self):
         """Parameter names in the order of the reference module's `.parameters()` (= its state_dict order): the
         integer keys of torch.optim.Adam.state_dict()['state'] index this list."""
         return [n for n in self.state_dict().keys() if n not in self.buffers]  # (buffers are no parameters)
+
+    def parameter_count(self):
+        return len(self.parameter_order())
 
     def adam_state_dict(self, exp_avg, exp_avg_sq, step, cfg=None):
         """The layout of `torch.optim.Adam(net.parameters()).state_dict()` — what the reference stores per optimiser

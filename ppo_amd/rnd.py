@@ -267,6 +267,19 @@ class RNDNets:
                    self.adam_steps, float(lr), float(beta1), float(beta2), float(eps), float(max_grad_norm), float(grad_div), _p(ws),
                    _p(grad_norm_out))
 
+    def sgd_step(self, lr=2.5e-4, max_grad_norm=20.0, grad_div=1.0, grad_norm_out: Optional[torch.Tensor] = None):
+        """Runner.optimizer_step(rnd_optimizer) under --rnd_opt_optimizer=sgd (rl/rollout.py:137-138, :1287-1321):
+        clip_grad_norm_ + torch.optim.SGD.step over the predictor's flat buffer; no moments, no step count."""
+        self._presummed = 0
+        net = self.prediction_net
+        nbytes = int(self.lib.ppo_adam_workspace_bytes())
+        ws = self._buf("adam_ws", ((nbytes + 3) // 4,))
+        self._call("ppo_sgd_step_f32", _p(net.flat), _p(net.grad), net.flat.numel(), float(lr), float(max_grad_norm),
+                   float(grad_div), _p(ws), _p(grad_norm_out))
+
+    def parameter_count(self):
+        return len(self.prediction_net.offsets)
+
     # ------------------------------------------------------------------ optimiser state (checkpoints)
     def optimizer_state_dict(self, cfg=None):
         """`torch.optim.Adam(prediction_net.parameters()).state_dict()` layout, as DualHeadNet.adam_state_dict writes it

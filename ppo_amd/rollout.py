@@ -45,7 +45,7 @@ import torch
 
 from . import _lib, parallel, sns, value_quality
 from .config import args
-from .models import AdamState
+from .models import AdamState, check_optimizer_layout, sgd_state_dict
 from .returns import calculate_bootstrapped_returns
 from .running_stats import RunningMeanStd
 
@@ -73,21 +73,34 @@ def intrinsic_return_scale(ems_norm, rms, int_rewards, terminals, gamma_int, pro
 
 class Optimizer:
     """What the reference's `self.policy_optimizer` etc. stand for here: a net's flat parameter buffer, one
-    set of Adam moments over it and the flag group with its hyper-parameters (rl/rollout.py:126-141)."""
+    set of Adam moments over it and the flag group with its hyper-parameters (rl/rollout.py:126-141).  `kind`: 'adam' or
+    'sgd', the flag group's --*_opt_optimizer unless given (the distil phase on the policy optimiser takes that
+    optimiser's kind along with its state).  An SGD optimiser has no state: `state` stays None and the net's own moments
+    are never allocated by it."""
 
-    def __init__(self, net, cfg, state=None):
+    def __init__(self, net, cfg, state=None, kind=None):
         self.net, self.cfg, self.state = net, cfg, state
+        self.kind = kind if kind is not None else cfg.optimizer
+        if self.kind not in ("adam", "sgd"):
+            raise ValueError(f"Invalid Optimizer {self.kind}")  # make_optimizer's message (rl/rollout.py:139-141)
 
     def zero_grad(self, set_to_none=True):
         self.net.grad.zero_()
 
     def state_dict(self):
-        """`torch.optim.Adam.state_dict()` layout, as the reference checkpoints it (rl/rollout.py:412-421)."""
+        """`torch.optim.Adam.state_dict()` (or `torch.optim.SGD.state_dict()`) layout, as the reference checkpoints it
+        (rl/rollout.py:412-421)."""
+        if self.kind == "sgd":
+            return sgd_state_dict(self.net.parameter_count(), self.cfg.lr)
         if self.state is None:
             return self.net.optimizer_state_dict(self.cfg)
         return self.net.adam_state_dict(self.state.exp_avg, self.state.exp_avg_sq, self.state.step, self.cfg)
 
     def load_state_dict(self, sd):
+        """A dict of the other kind is refused (torch would load it and carry on with the wrong hyper-parameters)."""
+        check_optimizer_layout(sd, self.kind)
+        if self.kind == "sgd":
+            return  # no state; lr comes from the flags, as for Adam
         if self.state is None:
             self.net.load_optimizer_state_dict(sd)
         else:
@@ -244,7 +257,8 @@ class Runner:
         # as the reference (rl/rollout.py:145-148): present whenever the distil phase has its own optimiser configured,
         # whatever the architecture (only `dual` ever steps it; its moment buffers are allocated on first use)
         own_distil = args.distil_opt.epochs > 0 and not args.distil.use_policy_opt
-        self.distil_optimizer = Optimizer(self.policy_net, args.distil_opt, AdamState()) if own_distil else None
+        distil_state = AdamState() if args.distil_opt.optimizer == "adam" else None  # an SGD optimiser has no state object
+        self.distil_optimizer = Optimizer(self.policy_net, args.distil_opt, distil_state) if own_distil else None
         self.rnd_optimizer = Optimizer(self.rnd, args.rnd_opt) if self.rnd is not None else None  # :154-157
         # ---- device scratch
         self._moments = torch.zeros(3, dtype=torch.float64, device=dev)
@@ -306,8 +320,9 @@ class Runner:
             for t in (net.exp_avg, net.exp_avg_sq):
                 if t is not None:
                     tensors.append(t)
-        if self.distil_optimizer is not None and self.distil_optimizer.state.exp_avg is not None:
-            tensors += [self.distil_optimizer.state.exp_avg, self.distil_optimizer.state.exp_avg_sq]
+        distil_state = self.distil_optimizer.state if self.distil_optimizer is not None else None  # None: SGD, nothing to send
+        if distil_state is not None and distil_state.exp_avg is not None:
+            tensors += [distil_state.exp_avg, distil_state.exp_avg_sq]
         rnd = self.rnd
         if rnd is not None:
             # the target is never trained, so replicas that drew their own would disagree for good; the predictor as the
@@ -1056,17 +1071,20 @@ class Runner:
             self.norm_advantage.clamp_(-args.advantage_clipping, args.advantage_clipping)
 
     def optimizer_step(self, optimizer=None, label="policy", norm_out=None):
-        """All-reduce (DP) + global-norm clip + Adam in the flat buffer (rl/rollout.py:1287-1321)."""
+        """All-reduce (DP) + global-norm clip + Adam or SGD in the flat buffer (rl/rollout.py:1287-1321)."""
         opt = optimizer or self.policy_optimizer
         net, cfg = opt.net, opt.cfg
         red = self._reducers.get(id(net))
         if red is not None:
             red.finish()  # late bucket + join of the early one that left during the backward pass
-        net.adam_step(lr=self._lr(cfg), beta1=cfg.adam_beta1, beta2=cfg.adam_beta2, eps=cfg.adam_epsilon,
-                      max_grad_norm=args.max_grad_norm if args.grad_clip_mode == "global_norm" else 0.0,
-                      grad_div=float(self.world), grad_norm_out=self._grad_norm if norm_out is None else norm_out,
-                      state=opt.state)
-        return self._grad_norm if norm_out is None else norm_out
+        max_grad_norm = args.max_grad_norm if args.grad_clip_mode == "global_norm" else 0.0
+        norm = self._grad_norm if norm_out is None else norm_out
+        if opt.kind == "sgd":
+            net.sgd_step(lr=self._lr(cfg), max_grad_norm=max_grad_norm, grad_div=float(self.world), grad_norm_out=norm)
+        else:
+            net.adam_step(lr=self._lr(cfg), beta1=cfg.adam_beta1, beta2=cfg.adam_beta2, eps=cfg.adam_epsilon,
+                          max_grad_norm=max_grad_norm, grad_div=float(self.world), grad_norm_out=norm, state=opt.state)
+        return norm
 
     def _micro_batches(self, mb, force_micro_batch_size=None):
         """(micro-batch size, count) of a per-rank minibatch of mb samples (rl/rollout.py:2310-2316): the reference
@@ -1515,7 +1533,7 @@ class Runner:
                                      pred_actions=batch.get("distil_actions"), loss_scale=loss_scale, index=idx, **kw)
         opt = self.policy_optimizer if args.distil.use_policy_opt else self.distil_optimizer
         # (with a replay buffer the batch is the sample drawn from it, otherwise the rollout where it lies)
-        self._run_epochs("distil", Optimizer(net, args.distil_opt, opt.state), args.distil_opt.epochs,
+        self._run_epochs("distil", Optimizer(net, args.distil_opt, opt.state, kind=opt.kind), args.distil_opt.epochs,
                          args.distil_opt.mini_batch_size, step, 4, obs=batch.get("prev_state"))
 
     def train_rnd(self):
